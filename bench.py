@@ -14,13 +14,24 @@ N>1    : one process per GPU (torchrun); utterances are independent, so each ran
          --split folds: strong scaling instead -- the --utts-per-gpu utterances of ONE job have
          their fold rows cut evenly over the N GPUs (single-utterance split, SURVEY §8e;
          wrnn_set_fold_ranges), the rows gathered to rank 0 as above; a latency mode.
-Also reported: roofline of the dominant recurrent kernel (HIP events on its stream over the
-timed region; HBM, fp32 and latency-floor fractions), the CPU baseline (oracle restatement of
-the reference generate() on this host: the whole utterance on the default thread count, plus
-bounded 1-thread and all-core legs; rank 0 after the timed region -- at N>1 on an utterance of the
-last rank) and `parity`: the timed call's labels and waveform against that same oracle run (same
-seed and noise stream). `config.lib_build` names the timed HIP library (SHA-256 prefix);
-`roofline.traffic_lib_build` the library the PMC counters were read from.
+A plain run sets up, warms up, times the --steps steps and prints the result line. The line also
+carries the roofline of the dominant recurrent kernel (HIP events on its stream over the timed
+region; HBM, fp32 and latency-floor fractions: no run of its own). `config.lib_build` names the
+timed HIP library (SHA-256 prefix); `roofline.traffic_lib_build` the library the PMC counters
+were read from.
+--full : after the timed region, the legs that take runs of their own: `dropin_host_io` (the
+         host-buffer API, two more calls), the CPU baseline (oracle restatement of the reference
+         generate() on this host: the whole utterance on the default thread count, plus bounded
+         1-thread and all-core legs; rank 0 -- at N>1 on an utterance of the last rank) and
+         `parity`: the timed call's labels and waveform against that same oracle run (same seed
+         and noise stream), with the teacher-forced logit gate (one more GPU call). --cpu-seconds
+         sizes the bounded legs (0 disables them all, as before).
+--dump-outputs DIR : what the last timed step returned to its caller, as DIR/<name>.npy (rank
+         0): wav_<u> the f64 waveform of utterance u, rows_<u> its fold rows (labels or float
+         samples, as float32). Inputs, weights and noise streams are functions of the arguments
+         alone, so two builds can be compared file by file. Above DUMP_LIMIT_BYTES in all, every
+         array is cut to the same fraction of its elements, drawn by a fixed seed
+         (<name>.npy then holds those elements in index order).
 """
 import argparse
 import json
@@ -48,8 +59,13 @@ def parse():
     ap.add_argument('--bits', type=int, default=9)
     ap.add_argument('--target', type=int, default=11000)
     ap.add_argument('--overlap', type=int, default=550)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the drop-in host-API leg, the CPU '
+                         'baseline, parity against the oracle and the logit gate')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's waveforms and fold rows as DIR/<name>.npy")
     ap.add_argument('--cpu-seconds', type=float, default=15.0,
-                    help='CPU-baseline sample budget (0 disables)')
+                    help='with --full: CPU-baseline sample budget (0 disables the --full legs)')
     ap.add_argument('--no-timing', action='store_true', help='disable kernel timing')
     ap.add_argument('--prune', type=float, default=0.0,
                     help='prune the synthetic weights as the reference Pruner does at this '
@@ -96,6 +112,31 @@ def lib_build_id():
             return hashlib.sha256(f.read()).hexdigest()[:16]
     except OSError:
         return None
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, wavs, rows):
+    """--dump-outputs: utterance u's waveform (float64) and fold rows (int16 labels or float32
+    samples, written as float32) of the last timed step as wav_<u>.npy / rows_<u>.npy. When
+    they exceed DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its elements:
+    a sample without replacement drawn by a generator seeded with the array's position, the
+    elements in index order."""
+    import numpy as np
+    arrays = []
+    for u, w in enumerate(wavs):
+        arrays.append((f'wav_{u:04d}', np.ascontiguousarray(w, dtype=np.float64)))
+        if u in rows:
+            arrays.append((f'rows_{u:04d}', np.ascontiguousarray(rows[u], dtype=np.float32)))
+    total = sum(a.nbytes + 128 for _, a in arrays)  # (.npy header)
+    os.makedirs(path, exist_ok=True)
+    for i, (name, a) in enumerate(arrays):
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(a.size * (DUMP_LIMIT_BYTES / total) * 0.99)
+            idx = np.sort(np.random.default_rng(i).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def _cpu_model():
@@ -379,6 +420,8 @@ def main():
         assert wavs is not None and sum(len(w) for w in wavs) == samples_per_step
     total_samples = samples_per_step * args.steps
     value = total_samples / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, wavs, last['rows'])
 
     wname = ('MOL' if hp.mode == 'MOL' else 'RAW (Beta)' if args.model == 'geneing-wavernn' and hp.mode == 'RAW'
              else f'{args.mode} {args.bits}-bit' + (' mu-law' if hp.mu_law else ''))
@@ -510,7 +553,8 @@ def main():
         result['ranks'] = ranks
     if fb[0]:
         result['config']['fallback_reason'] = fb[1]
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    extras = args.full and args.cpu_seconds > 0  # the legs that take runs of their own
+    if rank == 0 and world == 1 and extras:
         # parity of the last timed call: utterance 0's fold rows and waveform against the oracle
         gpu_rows = last['rows'][0]
         stream = last['base']
@@ -533,7 +577,7 @@ def main():
                                                                 gpu_rows, wavs[0], seed, stream)
         result['parity']['logits'] = logit_gate(args, sd, hp, model, mels[0], mels_host[0],
                                                 gpu_rows, seed, stream)
-    elif rank == 0 and world > 1 and args.cpu_seconds > 0:
+    elif rank == 0 and world > 1 and extras:
         # N > 1: the same CPU legs as N = 1, after the timed region and its barrier, on one
         # utterance of the LAST rank's shard (gathered over RCCL): the whole-utterance oracle leg
         # is also that utterance's parity check on its global stream (world-size invariance:

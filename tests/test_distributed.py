@@ -119,11 +119,19 @@ def _run(world, mode, split='utterance'):
 def _single_process(mode):
     from oracle.wavernn_oracle import oracle_infer_waveform
     from wavernn_amd.synth import synth_state_dict, synth_mel
+    import torch
     hp = _hp(mode)
     sd = synth_state_dict(hp, 'fatchord-wavernn', seed=1)
-    return [oracle_infer_waveform(sd, hp, 'fatchord-wavernn', synth_mel(T, seed=10 + i),
-                                  target=400, overlap=50, seed=5, stream=STREAM_BASE + i)['wav']
-            for i, T in enumerate(FRAMES[mode])]
+    # one thread, as the workers: the oracle's float (MOL) samples depend on how torch splits
+    # its reductions over threads, so the two sides must run on the same count
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        return [oracle_infer_waveform(sd, hp, 'fatchord-wavernn', synth_mel(T, seed=10 + i),
+                                      target=400, overlap=50, seed=5, stream=STREAM_BASE + i)['wav']
+                for i, T in enumerate(FRAMES[mode])]
+    finally:
+        torch.set_num_threads(threads)
 
 
 def test_two_rank_gather_equals_single_process():

@@ -2,7 +2,10 @@
 
 Fixtures: tests/golden/gen_e2e_golden.py ran the reference's own SpeakerEncoder, Tacotron and
 text front end on the same seeded weights / inputs (Tacotron prenet dropout from the shared
-``DropoutStream``). The PyTorch CPU kernels are the same, so equality is exact.
+``DropoutStream``). The PyTorch CPU ops are the same; the order in which the host's BLAS sums a
+matrix product depends on its CPU, so the float outputs are held to 1e-5 x max(1, max |ref|)
+(the fp32 bar of tests/test_gpu_logits.py; exact on the host that wrote the fixtures), shapes
+and the dropout call count exactly.
 """
 import json
 import os
@@ -15,6 +18,12 @@ from conftest import GOLDEN
 
 G = np.load(os.path.join(GOLDEN, 'e2e_models.npz'))
 TACO_SEED, ENC_SEED, DROP_SEED, STEPS = (int(v) for v in G['seeds'])
+FP32_ABS_TOL = 1e-5
+
+
+def assert_fp32_close(got, ref):
+    assert got.shape == ref.shape and got.dtype == ref.dtype
+    np.testing.assert_allclose(got, ref, rtol=0, atol=FP32_ABS_TOL * max(1.0, float(np.abs(ref).max())))
 
 
 def tacotron(device='cpu'):
@@ -45,9 +54,9 @@ def test_tacotron_generate_matches_reference():
     mel, lin, attn, calls = run_tacotron()
     assert calls == int(G['dropout_calls'][0])
     assert mel.shape == G['mel_out'].shape and lin.shape == G['linear'].shape
-    np.testing.assert_array_equal(mel, G['mel_out'])
-    np.testing.assert_array_equal(lin, G['linear'])
-    np.testing.assert_array_equal(attn, G['attn'])
+    assert_fp32_close(mel, G['mel_out'])
+    assert_fp32_close(lin, G['linear'])
+    assert_fp32_close(attn, G['attn'])
 
 
 def test_speaker_encoder_matches_reference():
@@ -58,7 +67,7 @@ def test_speaker_encoder_matches_reference():
     frames = np.random.default_rng(int(G['enc_frames_seed'][0])).uniform(0, 2, (3, 160, 40)).astype(np.float32)
     with torch.no_grad():
         e = m(torch.from_numpy(frames)).numpy()
-    np.testing.assert_array_equal(e, G['enc_embeds'])
+    assert_fp32_close(e, G['enc_embeds'])
 
 
 def test_text_to_sequence_matches_reference():

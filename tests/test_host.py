@@ -80,8 +80,12 @@ def test_short_mel_raises_like_reference():
         postprocess(np.zeros((1, 1200), np.float32), False, None, None, True, True, 512, 1000, 200)
 
 
-def test_inference_api_surface():
+def test_inference_api_surface(monkeypatch):
     from wavernn_amd import inference
+    # the module as a fresh process has it: a GPU test earlier in the same run (the whole suite
+    # on a GPU machine) leaves its vocoder loaded in the module's globals
+    monkeypatch.setattr(inference, '_model', None)
+    monkeypatch.setattr(inference, '_model_type', None)
     assert not inference.is_loaded()
     with pytest.raises(Exception, match='Please load Wave-RNN'):
         inference.infer_waveform(np.zeros((80, 10), np.float32))

@@ -15,7 +15,7 @@ run() {  # run <name> <timeout> cmd...
 }
 B="python bench.py --steps 3 --warmup 1 --cpu-seconds 0"
 S=${STEPS:-bench,mol,rr9,rr10,rrmol,gen,genmol,beta,c4,c4p,wide,tests,smoke}
-[[ ,$S, == *,bench,* ]] && run bench 300 python bench.py --steps 3 --warmup 1 --cpu-seconds 12
+[[ ,$S, == *,bench,* ]] && run bench 300 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 12
 [[ ,$S, == *,mol,* ]] && run mol 300 $B --mode MOL
 [[ ,$S, == *,rr9,* ]] && run rr9 300 $B --model runtimeracer-wavernn --bits 9
 [[ ,$S, == *,rr10,* ]] && run rr10 300 $B --model runtimeracer-wavernn --bits 10 --target 6000 --overlap 1000

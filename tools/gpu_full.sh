@@ -10,7 +10,7 @@ echo "tests rc=$rc"
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 echo "smoke rc=$?"; tail -2 $OUT/smoke.log
-timeout -k 10 300 python -u bench.py > $OUT/bench.log 2>&1
+timeout -k 10 300 python -u bench.py --full > $OUT/bench.log 2>&1
 echo "bench rc=$?"
 python - $OUT/bench.log <<'PY'
 import json,sys
