@@ -138,7 +138,12 @@ int wrnn_get_stream(wrnn_handle* h, uint32_t* stream);
  * world-size invariant: every rank gives utterance i of the global batch the stream
  * (base + i), as the reference's CPU backend seeds every worker instance explicitly
  * (vocoder/libwavernn/inference.py:106-108, :200-204). A count that does not match the
- * call's n_utts makes that call fail with WRNN_ERR_INVALID. */
+ * call's n_utts makes that call fail with WRNN_ERR_INVALID.
+ * MOL: the samples are floats, and a row run by a wide MFMA launch differs in rounding from
+ * the same row run by a register-resident launch (another summation order; RAW hides that
+ * behind exact labels). A shard's rows equal the single-GPU call's bit for bit only when both
+ * calls plan the same kernel family (wrnn_plan_info); env WRNN_PERSIST_WIDE=0 keeps every MOL
+ * call on the register-resident kernels and restores the strict form. */
 int wrnn_set_utt_streams(wrnn_handle* h, const uint32_t* streams, int n);
 /* Fold range of each utterance of the NEXT wrnn_generate_batch_device call only (n = its
  * n_utts; n = 0 clears): utterance u runs only its fold rows lo[u] .. hi[u] - 1 (0 <= lo < hi
@@ -148,7 +153,12 @@ int wrnn_set_utt_streams(wrnn_handle* h, const uint32_t* streams, int n);
  * global fold index) -- so the fold rows of one utterance can be split over ranks and the
  * union equals the single-call rows bit for bit (the "one exchange step" single-utterance
  * split of SURVEY §8e). The reference has no such call: its folds always run as one batch
- * (fatchord_version.py:180-187). wrnn_generate refuses an armed range. */
+ * (fatchord_version.py:180-187). wrnn_generate refuses an armed range.
+ * MOL: "bit for bit" holds when the piece and the whole call plan the same kernel family
+ * (register-resident or wide, wrnn_plan_info): the float samples of a wide launch differ in
+ * rounding from a register-resident launch's. Calls of at most 32 MOL rows stay
+ * register-resident under the shipped rates; WRNN_PERSIST_WIDE=0 restores the strict form for
+ * every size. */
 int wrnn_set_fold_ranges(wrnn_handle* h, const int* lo, const int* hi, int n);
 
 /* Fold arithmetic of fold_with_overlap for a mel of n_frames frames
@@ -207,7 +217,9 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap);
 /* Host-only launch plan (no device): the plan wrnn_generate would make for `rows` fold rows of
  * `seq_len` steps of a model_type / bits / mode model under the rate table `table` (NULL: the
  * built-in defaults), every kernel variant taken as spill-free. flags: 1 sparse image, 2 P1 ring /
- * per-frame P1, 4 wide images, 8 sparse forced (WRNN_SPARSE=1). Outputs: launches, rows per group and wide flag of the first `cap`,
+ * per-frame P1, 4 wide images (fatchord RAW and MOL, runtimeracer RAW), 8 sparse forced
+ * (WRNN_SPARSE=1). bits outside 1..10, an unknown mode or more than 2^20 rows are
+ * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag of the first `cap`,
  * and the row rotation's launch count (0: none). */
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
                     int* n_launches, int* rows_per_group, int* wide, int cap, int* rot_launches);
@@ -293,6 +305,11 @@ int wrnn_persist_steps(wrnn_handle* h, int stage, double* steps_per_launch);
  * expects its (row, unit quad), aligned, inside its slot; no-packet offsets out of range),
  * or WRNN_ERR_INVALID. No device needed. */
 int wrnn_debug_wide_layout(int rows_per_group);
+/* The same for the MOL head's use of the candidate area (wide_layout.h logit_off): violations
+ * among the (row, logit) tagged pairs of a group of `rows_per_group` rows -- each 8-byte
+ * aligned inside the area, written by exactly one fc3 epilogue lane and read by exactly one
+ * hop-D lane that expects that (row, logit) -- or WRNN_ERR_INVALID. No device needed. */
+int wrnn_debug_wide_mol_layout(int rows_per_group);
 
 /* Raw access for tests: copy the RAW noise (seq_len, rows, n_classes) of the last call's
  * first `n_steps` steps to host (float32). */

@@ -13,7 +13,8 @@
 //    (W_ih2[:, :512] r/z/n, W_hh1 r/z/n, fc1, fc2, fc3), W_hh2 r/z/n in LDS.
 //  * GRU1 distributed, not redundant: each slot runs GRU1 for its own 16 units x rows and
 //    publishes x1 / h1 (redundant GRU1 of all 512 units would cost 16x the cell work here).
-//    Five in-group hops per step: E (x1, h1), A (x2, h2), B (y1), C (y2), D (fc3 candidates).
+//    Five in-group hops per step: E (x1, h1), A (x2, h2), B (y1), C (y2), D (fc3 candidates;
+//    MOL: the 30 logits as tagged pairs, see the MOL template parameter).
 //  * Exchange: every published vector is laid out as 16-byte packets of 4 floats in MFMA
 //    B-operand order, two slots by step parity, so a consumer wave reads its B operand straight
 //    into registers with 4 fully coalesced 1-KiB loads per hop. Untagged: the slot a producer
@@ -190,8 +191,16 @@ __device__ __forceinline__ bool w_poll(rsrc_t xr, unsigned voff, unsigned so, bo
 //      first tile's MFMAs -- the registers hold the other nine tiles; its partials go to PH after
 //      one more barrier (the gh1 / gh2 partial sums are read in the hop-C wait instead of hop D,
 //      so PH is free by then)
-template <bool ROT, bool C10, bool DBG>
+// MOL: the mixture-of-logistics head (vocoder/distribution.py:104-140; 30 logits, slots 0 and 1
+//      of the fc3 tile layout). The fc3 epilogue publishes every logit as a tagged pair (float
+//      bits, seq) into the candidate area (wide_layout.h logit_off) -- no candidate key, no noise
+//      ring; in hop D the 16 lanes of a row poll the row's 30 pairs (lane cul: logits cul and
+//      16 + cul) and form the sample with k_persist<MOL>'s operations in its order, from the
+//      draws of k_mol_noise (a.gumbel [S][B][kMolNoise], lane cul < 12 holds draw cul of its row,
+//      loaded one step ahead). Every cell lane of the row then holds x. Excludes C10.
+template <bool ROT, bool C10, bool MOL, bool DBG>
 __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
+    static_assert(!(MOL && C10), "the MOL head has 30 logits: one fc3 tile");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // the whole 160 KiB
     int* sreg = reinterpret_cast<int*>(lds + WL_REG);
     const int tid = threadIdx.x;
@@ -337,7 +346,9 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
     //   pg (pg2) Gumbel noise of (row, class cu (512 + cu)) at step t (LDS ring, WL_GR)
     //   pp       P1(t + 1) of (row, unit cu), consumed by GRU1          (LDS ring, WL_P1R)
     //   pv       v = W_ih1 w0 (r, z, n) and w0 of unit cu         (constants, L1-resident)
+    //   MOL: pg is draw cul of the row at step t, pgn the one of step t + 1 (mol_draw)
     float pc[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, pg = 0.f, pg2 = 0.f;
+    [[maybe_unused]] float pgn = 0.f;
     float4 pp = make_float4(0.f, 0.f, 0.f, 0.f), pv = make_float4(0.f, 0.f, 0.f, 0.f);
     auto prefetch = [&](int t) {
         if (!cell) return;
@@ -356,7 +367,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
         if (!cell) return;
         int uu = cu;
         asm volatile("" : "+v"(uu));
-        pg = lds[WL_GR + cn * NC + cul];
+        if constexpr (!MOL) pg = lds[WL_GR + cn * NC + cul];
         if constexpr (C10) pg2 = lds[WL_GR + cn * NC + 16 + cul];
         pp = reinterpret_cast<const float4*>(lds + WL_P1R)[cn * 16 + cul];
         pv.x = bld(vr, (unsigned)uu * 4u, 0);
@@ -378,6 +389,18 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
     //    formed for step t + 2 in step t's hop-D window (GRU1 at the end of step t + 1 reads it).
     // (a time-sliced row at offset off: its own steps end at S, its noise is drawn at its
     // absolute step)
+    // MOL: draw cul of the cell's row at the row's absolute step te + off (clamped to the row's
+    // last step: the load of the step after the last is never used), from the k_mol_noise stream.
+    // One uniform base and a 32-bit lane offset (the planner keeps the stream below 2 GiB for a
+    // wide MOL launch, runtime.hip plan_call).
+    auto mol_draw = [&](int te) {
+        if (!cell || cul >= kMolNoise) return;
+        int nn = cn;
+        asm volatile("" : "+v"(nn));  // (recomputed per step: hoisted offsets cost registers)
+        const int2 vm = reinterpret_cast<const int2*>(lds + WL_VM)[nn];
+        const int tc = te < a.S - vm.y ? te : a.S - vm.y - 1;
+        pgn = bld(mk_rsrc(a.gumbel), (unsigned)(((tc + vm.y) * a.B + vm.x) * kMolNoise + cul) * 4u, 0);
+    };
     auto noise_make = [&](int n, int j, int tau) {
         const int off = ROT ? reinterpret_cast<const int2*>(lds + WL_VM)[n].y : 0;
         int uu = 16 * w + j;
@@ -445,8 +468,12 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
     // P1(t + 2) at step t); the first reads come after the barrier
     if (!lo && tid - 256 < 16 * R) {
         const int i = tid - 256;
-        noise_make(i >> 4, i & 15, a.t0);
+        if constexpr (!MOL) noise_make(i >> 4, i & 15, a.t0);
         p1_make(i >> 4, i & 15, a.t0 + 1);
+    }
+    if constexpr (MOL) {  // the draws of step t0 (the loop loads those of t + 1 at step t)
+        mol_draw(a.t0);
+        pg = pgn;
     }
     __syncthreads();
     // initial hop E: x1, h1 of step t0 (k_persist_init) as step t0 + 1 (canonicalised: a
@@ -644,6 +671,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
                                                                                          (unsigned)q * 1024u, 0));
         }
         if constexpr (!C10) prefetch_d();
+        if constexpr (MOL) mol_draw(t + 1);
         WSTAMP(8);
         {
             v4f acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -672,7 +700,18 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
             // fc3 epilogue: the candidate key (cand_key.h: l_k + G_k formed exactly as an fp32 pair)
             // of the slot's 16 classes per row, max over the row's DPP row of 16 lanes,
             // published with the step tag by lane cul == 0
-            {
+            if constexpr (MOL) {
+                // MOL: logit (row cn, index cu) as a tagged pair, polled directly in hop D (slots
+                // 0 and 1 hold the 30 logits; the other slots publish nothing)
+                if (cell && cu < a.n_classes) {
+                    float s;
+                    psums(I1(), WL_PS, 1, &s);
+                    const float lg = p_add(s, lds[WL_BIAS + 96 + cul]);
+                    p_dbg_logit<DBG>(a.dbg, t + (ROT ? reinterpret_cast<const int2*>(lds + WL_VM)[cn].y : 0), crow, cu,
+                                     a.B, a.n_classes, lg);
+                    bst_tag(lg, seq, xr, wide::logit_off(cn, cu), WX_D * 4);
+                }
+            } else {
                 uint32_t kh = 0, kl = 0;
                 if (cell && cu < a.n_classes) {
                     float s;
@@ -725,7 +764,61 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
             // lane (row cn, cul) reads the candidates of slots 2 cul, 2 cul + 1 of its row; the
             // row's 16 lanes reduce them (DPP), so every cell of the row holds the sample
             float x;
-            {
+            if constexpr (MOL) {
+                // lane (row cn, cul) polls logits cul and 16 + cul of its row (tag: the whole seq);
+                // a lane without a logit loads from an out-of-range offset (reads 0, not waited for)
+                const bool ra = cell && cul < a.n_classes, rb = cell && 16 + cul < a.n_classes;
+                unsigned va = ra ? wide::logit_off(cn, cul) : wide::kNoOffset;
+                unsigned vb = rb ? wide::logit_off(cn, 16 + cul) : wide::kNoOffset;
+                asm volatile("" : "+v"(va), "+v"(vb));
+                u2v qa, qb;
+                const unsigned t0s = p_now();
+                unsigned nsp = 0;
+                while (true) {
+                    qa = __builtin_amdgcn_raw_buffer_load_b64(xr, va, WX_D * 4, kCpNT);
+                    qb = __builtin_amdgcn_raw_buffer_load_b64(xr, vb, WX_D * 4, kCpNT);
+                    if (__all((!ra | (qa.y == seq)) & (!rb | (qb.y == seq)))) break;
+                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
+                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
+                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(9) | ((unsigned)v << 19)) == 0u)
+                            a.ctl[PC_WHERE + 2] = (unsigned)t;
+                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
+                        fail = true;
+                        break;
+                    }
+                }
+                // the sample: k_persist<MOL>'s operations in its order (kernels_persist.hip, "MOL:")
+                const float la = __uint_as_float(qa.x), lb = __uint_as_float(qb.x);
+                float bv;
+                {
+#pragma clang fp contract(off)
+                    bv = cul < 10 ? la - pg : -INFINITY;
+                }
+                int bi = cul < 10 ? cul : 0x7fffffff;
+                row16_argmax(bv, bi);  // first max over k < 10; every lane of the row gets it
+                bi = bi < 10 ? bi : 0;
+                const int base = l & 48;  // lane 0 of this lane's row
+                // l[10 + bi]: the first value of lane 10 + bi, or the second of lane bi - 6
+                const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
+                const float mean = bi < 6 ? m0 : m1;
+                float ls = __shfl(lb, base + 4 + bi);  // l[20 + bi]: the second value of lane 4 + bi
+                const float lu = __shfl(pg, base + 10);
+                {
+#pragma clang fp contract(off)
+                    const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
+                    ls = ls < lsmin ? lsmin : ls;
+                    x = mean + expf(ls) * lu;
+                    x = x < -1.f ? -1.f : x;
+                    x = x > 1.f ? 1.f : x;
+                }
+                pg = pgn;
+                if (w == 0 && cell && cul == 0) {
+                    int nn = cn;
+                    asm volatile("" : "+v"(nn));
+                    const int2 vm = reinterpret_cast<const int2*>(lds + WL_VM)[nn];
+                    bst(x, mk_rsrc(a.samples), (unsigned)(vm.x * a.ld + vm.y) * 4u, (unsigned)t * 4u);
+                }
+            } else {
                 const unsigned want = key_tag(seq);
                 u4v q = {0u, want, 0u, want};
                 const unsigned t0s = p_now();
@@ -784,7 +877,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
             // step's stage-A barrier)
             const int i = tid - 256;
             if (i < 16 * R) {
-                noise_make(i >> 4, i & 15, t + 1);
+                if constexpr (!MOL) noise_make(i >> 4, i & 15, t + 1);
                 p1_make(i >> 4, i & 15, t + 2);
             }
         }
@@ -882,36 +975,88 @@ int wide_layout_check(int R) {
 size_t persist_wide_wreg_floats() { return (size_t)kPM * 8 * 4 * kWTiles * 64 * 4; }
 size_t persist_wide_wlds_floats() { return (size_t)kPM * WL_HH2_SZ; }
 
-int persist_wide_scratch(bool c10) {
+// Host-side check of the MOL logit pairs in the candidate area for a group of R rows
+// (wide_layout.h logit_off): every (row, logit) pair is 8-byte aligned inside WX_CAND, written by
+// exactly one (slot, cell lane) of the fc3 epilogue (slot w, lane cul: logit 16 w + cul) and read
+// by exactly one hop-D lane of the row (lane cul: logits cul and 16 + cul), and no two pairs
+// overlap. Returns the violations.
+int wide_mol_layout_check(int R) {
+    using namespace wide;
+    if (R < 1 || R > kRows) return -1;
+    int bad = 0;
+    std::vector<int> wr(WX_CAND / 2, 0), rd(WX_CAND / 2, 0), id(WX_CAND / 2, -1);
+    for (int w = 0; w < kSlots; ++w)
+        for (int cn = 0; cn < R; ++cn)
+            for (int cul = 0; cul < 16; ++cul) {
+                const int k = 16 * w + cul;
+                if (k >= kMolLogits) continue;  // (the epilogue's `cu < n_classes`)
+                const unsigned o = logit_off(cn, k);
+                if (o % 8 || o + 8 > (unsigned)WX_CAND * 4u) { ++bad; continue; }
+                ++wr[o / 8];
+                id[o / 8] = cn * 32 + k;
+            }
+    for (int cn = 0; cn < R; ++cn)
+        for (int cul = 0; cul < 16; ++cul)
+            for (int k = cul; k < kMolLogits; k += 16) {
+                const unsigned o = logit_off(cn, k);
+                if (o % 8 || o + 8 > (unsigned)WX_CAND * 4u) { ++bad; continue; }
+                ++rd[o / 8];
+                if (id[o / 8] != cn * 32 + k) ++bad;  // the reader expects another (row, logit)
+            }
+    int pairs = 0;
+    for (int i = 0; i < WX_CAND / 2; ++i) {
+        if (wr[i] > 1 || rd[i] > 1 || wr[i] != rd[i]) ++bad;
+        pairs += wr[i];
+    }
+    if (pairs != R * kMolLogits) ++bad;
+    return bad;
+}
+
+int persist_wide_scratch(bool c10, bool mol) {
     hipFuncAttributes fa;
-    const void* f = c10 ? (const void*)k_persist_wide<false, true, false> : (const void*)k_persist_wide<false, false, false>;
+    const void* f = mol   ? (const void*)k_persist_wide<false, false, true, false>
+                    : c10 ? (const void*)k_persist_wide<false, true, false, false>
+                          : (const void*)k_persist_wide<false, false, false, false>;
     if (hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
     return (int)fa.localSizeBytes;
 }
-int persist_wide_rot_scratch(bool c10) {
+int persist_wide_rot_scratch(bool c10, bool mol) {
     hipFuncAttributes fa;
-    const void* f = c10 ? (const void*)k_persist_wide<true, true, false> : (const void*)k_persist_wide<true, false, false>;
+    const void* f = mol   ? (const void*)k_persist_wide<true, false, true, false>
+                    : c10 ? (const void*)k_persist_wide<true, true, false, false>
+                          : (const void*)k_persist_wide<true, false, false, false>;
     if (hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
     return (int)fa.localSizeBytes;
 }
 
 hipError_t launch_persist_wide(const PersistArgs& a, hipStream_t s) {
     if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || a.n_classes > 2 * kPM * 16 ||
-        a.mode != 0 || a.wwide == nullptr || (a.n_classes > kPM * 16 && a.wfc3b == nullptr))
+        (a.mode != 0 && a.mode != 1) || a.wwide == nullptr ||
+        (a.n_classes > kPM * 16 && a.wfc3b == nullptr))
         return hipErrorInvalidValue;
     const size_t lb = persist_wide_lds_bytes();
     const bool dbg = a.dbg.out != nullptr;
     if (a.vmap && a.p1q == nullptr) return hipErrorInvalidValue;  // time-sliced rows: P1 formed in-kernel
-    if (a.n_classes > kPM * 16) {
-        if (a.vmap) return dbg ? persist_launch<k_persist_wide<true, true, true>>(lb, a, s)
-                               : persist_launch<k_persist_wide<true, true, false>>(lb, a, s);
-        return dbg ? persist_launch<k_persist_wide<false, true, true>>(lb, a, s)
-                   : persist_launch<k_persist_wide<false, true, false>>(lb, a, s);
+    if (a.mode == 1) {  // MOL
+        // 30 logits in slots 0 and 1; the draws come from the k_mol_noise stream, indexed in 32 bits
+        if (a.n_classes != wide::kMolLogits || a.gumbel == nullptr ||
+            (double)a.S * a.B * kMolNoise * 4.0 >= 2147483648.0)
+            return hipErrorInvalidValue;
+        if (a.vmap) return dbg ? persist_launch<k_persist_wide<true, false, true, true>>(lb, a, s)
+                               : persist_launch<k_persist_wide<true, false, true, false>>(lb, a, s);
+        return dbg ? persist_launch<k_persist_wide<false, false, true, true>>(lb, a, s)
+                   : persist_launch<k_persist_wide<false, false, true, false>>(lb, a, s);
     }
-    if (a.vmap) return dbg ? persist_launch<k_persist_wide<true, false, true>>(lb, a, s)
-                           : persist_launch<k_persist_wide<true, false, false>>(lb, a, s);
-    return dbg ? persist_launch<k_persist_wide<false, false, true>>(lb, a, s)
-               : persist_launch<k_persist_wide<false, false, false>>(lb, a, s);
+    if (a.n_classes > kPM * 16) {
+        if (a.vmap) return dbg ? persist_launch<k_persist_wide<true, true, false, true>>(lb, a, s)
+                               : persist_launch<k_persist_wide<true, true, false, false>>(lb, a, s);
+        return dbg ? persist_launch<k_persist_wide<false, true, false, true>>(lb, a, s)
+                   : persist_launch<k_persist_wide<false, true, false, false>>(lb, a, s);
+    }
+    if (a.vmap) return dbg ? persist_launch<k_persist_wide<true, false, false, true>>(lb, a, s)
+                           : persist_launch<k_persist_wide<true, false, false, false>>(lb, a, s);
+    return dbg ? persist_launch<k_persist_wide<false, false, false, true>>(lb, a, s)
+               : persist_launch<k_persist_wide<false, false, false, false>>(lb, a, s);
 }
 
 }  // namespace wrnn

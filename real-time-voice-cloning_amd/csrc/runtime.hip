@@ -131,6 +131,9 @@ struct PlanRates {
     // 9.72 us at 16 rows (profiles/r05/final/c4.log, r06/b sp_c4), 10.965 at 16 rows / 1024
     // classes (r05/final/b10.log), 10.59 at 6 rows / 1024 classes (r06/b u10_wide)
     double wide[3] = {9.32, 0.025, 1.24};
+    // the MOL head on the wide kernel (fatchord): base + row x r. 9.43 / 9.57 / 9.65 us at 5 / 9 /
+    // 16 rows per group (profiles/wide_mol/mol_wide_r*.log, least squares: tools/make_rates.py)
+    double wide_mol[2] = {9.366, 0.0185};
     double wide_rr[2] = {12.0, 0.025};                     // 12.39 us at 15-16 rows (r04 wide_rr)
     double slice[2] = {60.0, 0.98};                        // us per extra launch, gain threshold
     // rotation: rates of the rotated instance's two bodies by rows per group (the (q + 1)-row
@@ -813,13 +816,15 @@ int pack_persist_sparse(wrnn_handle* h) {
 // lane l, tile T, k-step ks: W_T[row 16 w + (l & 15)][unit 64 v + 16 (l >> 4) + ks]; registers
 // [w][v][40 float4 (4 T + ks / 4)][64 l] for T = W_ih2[:, :512] r, z, n | W_hh1 r, z, n | fc1 |
 // fc2 | fc3 (x parts only), LDS [w][3 T][v][4 q][64 l][4] for W_hh2 r, z, n; above 512 classes
-// the second fc3 tile (rows 512 + 16 w + i) as [w][v][4 q][64 l] float4, read per step.
+// the second fc3 tile (rows 512 + 16 w + i) as [w][v][4 q][64 l] float4, read per step. MOL: the
+// 30 fc3 rows fill slots 0 and 1 of the same fc3 tile layout (rows u >= n are zero).
 int pack_persist_wide(wrnn_handle* h) {
     auto& T = h->host;
     auto& P = h->pw;
     P.wwide = P.wwide_lds = P.wfc3b = nullptr;
     const int H = h->H, F = h->F, A = h->A, n = h->n_classes;
-    if (h->cfg.mode != WRNN_MODE_RAW || n > 2 * kPM * 16 || H != kPH || F != kPH) return WRNN_OK;
+    const bool raw = h->cfg.mode == WRNN_MODE_RAW, mol = h->cfg.mode == WRNN_MODE_MOL && n <= 32;
+    if (!(raw || mol) || n > 2 * kPM * 16 || H != kPH || F != kPH) return WRNN_OK;
     const auto& Wih2 = T["rnn2.weight_ih_l0"];  // (3H, H + A)
     const auto& Whh1 = T["rnn1.weight_hh_l0"];  // (3H, H)
     const auto& Whh2 = T["rnn2.weight_hh_l0"];  // (3H, H)
@@ -2691,6 +2696,7 @@ static const RateKey kRateKeys[] = {
     {"rr", nullptr, &PlanRates::rr, nullptr, nullptr},
     {"gen", nullptr, &PlanRates::gen, nullptr, nullptr},
     {"wide", nullptr, nullptr, &PlanRates::wide, nullptr},
+    {"wide_mol", nullptr, nullptr, nullptr, &PlanRates::wide_mol},
     {"wide_rr", nullptr, nullptr, nullptr, &PlanRates::wide_rr},
     {"slice", nullptr, nullptr, nullptr, &PlanRates::slice},
     {"rot9", nullptr, &PlanRates::rot9, nullptr, nullptr},
@@ -2797,7 +2803,7 @@ struct PlanIn {
     int mode = 0, n = 0, cpw = 0, B = 0, S = 0;
     bool c10 = false, sp = false, p1ring = false, rr_frames = false;
     bool force_sp = false;  // env WRNN_SPARSE=1: the sparse instances whatever the rates
-    bool has_wide = false, has_wide_rr = false;
+    bool has_wide = false, has_wide_rr = false;  // (has_wide: RAW or MOL images; has_wide_rr: RAW only)
     int scr[2][kPNR + 1] = {};     // fatchord k_persist [stream | ring][nr]
     int scr_sp[kPNR + 1] = {};     // sparse instances
     int scr_rot[2][kPNR + 1] = {}; // rotated instance of this topology / mode [dense | sparse][nr]
@@ -2824,6 +2830,14 @@ struct PlanOut {
 void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
     out = PlanOut();
     const int B = in.B, S = in.S;
+    // per-step cost of a fatchord wide launch of r rows per group
+    const bool mol = in.mode == WRNN_MODE_MOL;
+    auto wide_us = [&](int r) {
+        return mol ? R.wide_mol[0] + R.wide_mol[1] * r : R.wide[0] + R.wide[1] * r + (in.c10 ? R.wide[2] : 0.0);
+    };
+    // a wide MOL launch indexes the k_mol_noise stream ([S][rows][kMolNoise], rows padded to a
+    // launch) in 32 bits: it must stay below 2 GiB (launch_persist_wide refuses it otherwise)
+    const bool wide_fits = !mol || (double)S * (B + kPG * kPWideRows) * kMolNoise * 4.0 < 2147483648.0;
     struct Opt {
         int nr;
         bool wide;
@@ -2862,10 +2876,9 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
                 }
                 if (sc >= 0 && sc <= 64) opts.push_back({c, false, us[c]});
             }
-            if (in.wmode && in.has_wide && (in.wide_scr == 0 || in.allow_wide_scratch)) {
+            if (in.wmode && in.has_wide && wide_fits && (in.wide_scr == 0 || in.allow_wide_scratch)) {
                 if (in.wmode == 1) opts.clear();
-                for (int r = 1; r <= kPWideRows; ++r)
-                    opts.push_back({r, true, R.wide[0] + R.wide[1] * r + (in.c10 ? R.wide[2] : 0.0)});
+                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, wide_us(r)});
             }
         } else {
             for (int r = 1; r <= kPNR; ++r)
@@ -2905,18 +2918,17 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
             out.plan_us = best[B];
         }
     }
-    // time-sliced wide launches, when cheaper than the plan above by the same rates (RAW, P1
-    // formed in-kernel: fatchord up to 1024 classes, runtimeracer)
-    const bool fat_sl = in.ok && in.fat && in.has_wide && in.p1ring;
-    const bool rr_sl = in.ok && in.rr && in.has_wide_rr && in.rr_frames;
-    if ((fat_sl || rr_sl) && in.mode == WRNN_MODE_RAW && !out.lplan.empty() && !in.slice_off && in.wmode &&
-        in.wide_rot_scr == 0) {
+    // time-sliced wide launches, when cheaper than the plan above by the same rates (P1 formed
+    // in-kernel: fatchord RAW up to 1024 classes and MOL, runtimeracer RAW)
+    const bool fat_sl = in.ok && in.fat && in.has_wide && in.p1ring && wide_fits &&
+                        (in.mode == WRNN_MODE_RAW || mol);
+    const bool rr_sl = in.ok && in.rr && in.has_wide_rr && in.rr_frames && in.mode == WRNN_MODE_RAW;
+    if ((fat_sl || rr_sl) && !out.lplan.empty() && !in.slice_off && in.wmode && in.wide_rot_scr == 0) {
         std::vector<wrnn_handle::WLaunch> sl;
         if (plan_wide_slices(B, S, sl)) {
             double cost = R.slice[0] * (sl.size() - 1);  // (an extra launch: weights, ring prologue)
             for (const auto& L : sl)
-                cost += L.steps * (fat_sl ? R.wide[0] + R.wide[1] * L.nr + (in.c10 ? R.wide[2] : 0.0)
-                                          : R.wide_rr[0] + R.wide_rr[1] * L.nr);
+                cost += L.steps * (fat_sl ? wide_us(L.nr) : R.wide_rr[0] + R.wide_rr[1] * L.nr);
             if (cost < R.slice[1] * out.plan_us * S) {
                 out.lplan.clear();
                 for (int j = 0; j < (int)sl.size(); ++j) out.lplan.push_back({0, sl[j].nr, true, j});
@@ -3017,8 +3029,8 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
         }
     }
     if (in.has_wide) {
-        in.wide_scr = persist_wide_scratch(in.c10);
-        in.wide_rot_scr = persist_wide_rot_scratch(in.c10);
+        in.wide_scr = persist_wide_scratch(in.c10, in.mode == WRNN_MODE_MOL);
+        in.wide_rot_scr = persist_wide_rot_scratch(in.c10, in.mode == WRNN_MODE_MOL);
     } else if (in.has_wide_rr) {
         in.wide_scr = persist_wide_rr_scratch();
         in.wide_rot_scr = persist_wide_rr_rot_scratch();
@@ -3663,6 +3675,12 @@ int wrnn_debug_wide_layout(int rows_per_group) {
     return bad + bad_rr;
 }
 
+int wrnn_debug_wide_mol_layout(int rows_per_group) {
+    const int bad = wide_mol_layout_check(rows_per_group);
+    if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..16");
+    return bad;
+}
+
 int wrnn_debug_beta(uint64_t seed, uint32_t stream, uint32_t step, uint32_t row, float alpha,
                     float beta, float* out) {
     if (!out) return fail(WRNN_ERR_INVALID, "null argument");
@@ -3720,10 +3738,16 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap) {
     return WRNN_OK;
 }
 
+constexpr int kPlanRowsMax = 1 << 20;  // wrnn_debug_plan: far above any call (C4 is 144 rows per GPU)
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
                     int* n_launches, int* rows_per_group, int* wide, int cap, int* rot_launches) {
     if (!n_launches || !rot_launches) return fail(WRNN_ERR_INVALID, "null argument");
     if (rows < 1 || seq_len < 1 || cap < 0) return fail(WRNN_ERR_INVALID, "bad arguments");
+    // (1 << bits below; the planner's tables have rows + 1 entries)
+    if (bits < 1 || bits > 10) return fail(WRNN_ERR_INVALID, "bits must be 1..10");
+    if (mode != WRNN_MODE_RAW && mode != WRNN_MODE_MOL && mode != WRNN_MODE_BETA)
+        return fail(WRNN_ERR_INVALID, "mode must be one of WRNN_MODE_*");
+    if (rows > kPlanRowsMax) return fail(WRNN_ERR_INVALID, "rows above " + std::to_string(kPlanRowsMax));
     PlanRates R;
     std::string err;
     if (table && !parse_rates(table, R, err)) return fail(WRNN_ERR_INVALID, "rate table: " + err);
@@ -3745,7 +3769,7 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     in.force_sp = in.sp && (flags & 8);
     in.p1ring = in.fat && (flags & 2);
     in.rr_frames = in.rr && (flags & 2);
-    in.has_wide = in.fat && (flags & 4) && mode == WRNN_MODE_RAW;
+    in.has_wide = in.fat && (flags & 4) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.has_wide_rr = in.rr && (flags & 4) && mode == WRNN_MODE_RAW;
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
     PlanOut out;

@@ -43,6 +43,13 @@ __host__ __device__ constexpr unsigned slot_base(int hb, unsigned s) {
 }
 // candidate of row n from slot w (8 bytes: value, step tag | class)
 __host__ __device__ constexpr unsigned cand_off(int n, int w) { return (unsigned)((n * kSlots + w) * 2) * 4u; }
+// MOL launches use the candidate area for the rows' logits instead: logit k (< kMolLogits) of
+// row n as a tagged pair (8 bytes: float bits, step tag = the whole seq), written by cell lane
+// k % 16 of slot k / 16, polled by lane k % 16 of row n in every slot (wide_mol_layout_check)
+constexpr int kMolLogits = 30;      // 10 mixture logits, 10 means, 10 log-scales
+__host__ __device__ constexpr unsigned logit_off(int n, int k) { return (unsigned)((n * 32 + k) * 2) * 4u; }
+static_assert(kMolLogits <= 32 && logit_off(kRows - 1, 31) + 8 == (unsigned)WX_CAND * 4u,
+              "16 rows x 32 logit pairs are exactly the candidate area");
 
 static_assert(WX_GROUP % 4 == 0 && WX_D % 4 == 0, "reset works in 16-byte units");
 static_assert(kNoOffset > kRsrcRecords, "the no-packet offset must fail the range check");

@@ -270,9 +270,10 @@ hipError_t persist_wide_reset_xbuf(float* xbuf, hipStream_t s);
 size_t persist_wide_ring_floats();
 size_t persist_wide_wreg_floats();
 size_t persist_wide_wlds_floats();
-int persist_wide_scratch(bool c10 = false);      // (c10: the 1024-class instances)
-int persist_wide_rot_scratch(bool c10 = false);  // the time-sliced instance (PersistArgs::vmap)
+int persist_wide_scratch(bool c10 = false, bool mol = false);      // (c10: the 1024-class instances; mol: the MOL head's)
+int persist_wide_rot_scratch(bool c10 = false, bool mol = false);  // the time-sliced instance (PersistArgs::vmap)
 int wide_layout_check(int rows_per_group);  // host: violations of the exchange layout (wide_layout.h)
+int wide_mol_layout_check(int rows_per_group);  // host: violations of the MOL logit-pair layout
 hipError_t launch_persist_init(const PersistArgs& a, hipStream_t s);
 constexpr int kMolNoise = 12;  // floats per (step, row) of the precomputed MOL noise
 // ---------------------------------------------------------------------------------------

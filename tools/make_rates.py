@@ -12,6 +12,8 @@ time) and writes `key v1 .. v4` lines for the keys it found; the runtime
   <dir>/rr_nr<k>.log   -> rr        <dir>/gen_nr<k>.log -> gen
   <dir>/c4.log (16 rows / group, 512 classes), <dir>/b10.log (16 rows, 1024 classes),
   <dir>/u10_wide.log (6 rows, 1024 classes) -> wide = base, per row, 1024-class extra
+  <dir>/mol_wide_r<k>.log (fatchord MOL, every launch wide at k rows per group, WRNN_PERSIST_WIDE=1;
+    at least two fills, e.g. k = 5 and 16) -> wide_mol = base, per row (least squares)
 Later directories override earlier ones. The rotation tables keep the runtime's defaults unless
 a key is already in the file given as OUT (kept lines are carried over).
 """
@@ -53,6 +55,14 @@ def main():
             per_row = max(per_row, 0.001)
             keys['wide'] = [round(c4 - 16 * per_row, 3), round(per_row, 4), round(extra, 3)]
             src['wide'] = d
+        pts = [(k, us_step(line_of(os.path.join(d, f'mol_wide_r{k}.log')))) for k in range(1, 17)]
+        pts = [(k, v) for k, v in pts if v is not None]
+        if len(pts) >= 2:
+            mk, mv = sum(k for k, _ in pts) / len(pts), sum(v for _, v in pts) / len(pts)
+            per_row = sum((k - mk) * (v - mv) for k, v in pts) / sum((k - mk) ** 2 for k, _ in pts)
+            per_row = max(per_row, 0.001)
+            keys['wide_mol'] = [round(mv - per_row * mk, 3), round(per_row, 4)]
+            src['wide_mol'] = d
     kept = []
     if os.path.exists(out):
         for ln in open(out):
