@@ -217,8 +217,9 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap);
 /* Host-only launch plan (no device): the plan wrnn_generate would make for `rows` fold rows of
  * `seq_len` steps of a model_type / bits / mode model under the rate table `table` (NULL: the
  * built-in defaults), every kernel variant taken as spill-free. flags: 1 sparse image, 2 P1 ring /
- * per-frame P1, 4 wide images (fatchord RAW and MOL, runtimeracer RAW), 8 sparse forced
- * (WRNN_SPARSE=1). bits outside 1..10, an unknown mode or more than 2^20 rows are
+ * per-frame P1, 4 wide images (fatchord RAW and MOL, runtimeracer RAW, geneing BITS with 512 or
+ * 1024 classes; geneing MOL / Beta have no wide launch, and geneing calls of at most 32 rows plan
+ * none unless forced), 8 sparse forced (WRNN_SPARSE=1). bits outside 1..10, an unknown mode or more than 2^20 rows are
  * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag of the first `cap`,
  * and the row rotation's launch count (0: none). */
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
@@ -310,6 +311,10 @@ int wrnn_debug_wide_layout(int rows_per_group);
  * aligned inside the area, written by exactly one fc3 epilogue lane and read by exactly one
  * hop-D lane that expects that (row, logit) -- or WRNN_ERR_INVALID. No device needed. */
 int wrnn_debug_wide_mol_layout(int rows_per_group);
+/* The same for the geneing wide launch (kernels_persist_wide_gen.hip): violations among the x1 /
+ * h1 packets (256 units), the y1 packets (128 units) and the candidate pairs of a group of
+ * `rows_per_group` rows (1..16), or WRNN_ERR_INVALID. No device needed. */
+int wrnn_debug_wide_gen_layout(int rows_per_group);
 
 /* Raw access for tests: copy the RAW noise (seq_len, rows, n_classes) of the last call's
  * first `n_steps` steps to host (float32). */

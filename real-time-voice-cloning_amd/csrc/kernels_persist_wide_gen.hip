@@ -1,0 +1,494 @@
+// Persistent geneing recurrence for WIDE row batches (launch kind "persist-wide" of the geneing
+// topology): up to 16 fold rows per XCD group, 128 rows per launch, every product on the fp32
+// matrix cores (v_mfma_f32_16x16x4_f32). geneing 'BITS' (WRNN_MODE_RAW), 512 or 1024 classes;
+// MOL and Beta stay on k_persist_gen.
+//
+// Reference step body: vocoder/models/geneing_version.py:193-205 (rnn_dims 256, fc_dims 128):
+//   x1 = I(x0) + h1'     h1' = rnn1(I(x0), h1)
+//   y1 = relu(fc1([x1, a2]))        logits = fc3(y1) -> categorical draw
+// restructured as kernels_persist_gen.hip (conditioning per frame, P1 + v x for GRU1's input,
+// torch-form gate math with contraction off).
+//
+// Layout: the 32 slots of an XCD group are alike (no halves: the step is one chain, so a split
+// in two halves would leave one half idle and give each busy slot twice the tiles). Slot w owns
+// GRU units [8 w, 8 w + 8), fc1 outputs [4 w, 4 w + 4) and fc3 classes [cpw w, cpw (w + 1)),
+// cpw = n / 32 (16 or 32). Its five MFMA A tiles (16 rows each):
+//   T0  W_hh1 gate r of the 8 units (m < 8) | gate z (m >= 8)          K = 256
+//   T1  W_hh1 gate n of the 8 units (m < 8) | zero                     K = 256
+//   T2  fc1[:, :256] rows 4 w + m (m < 4) | zero                       K = 256
+//   T3, T4  fc3 rows cpw w + 16 j + m (j < cpw / 16)                   K = 128
+// (T1 and T2 are half and three quarters empty: 32 MFMAs per wave and step in all, against 40
+// for a two-half split with full tiles.) K is split over the 8 waves (K = 256: wave v takes
+// inputs [32 v, 32 v + 32), 8 k-steps of 4; K = 128: [16 v, 16 v + 16), 4 k-steps), the 8
+// partial tiles are summed in LDS in a fixed order (v = 0 .. 7) by the epilogue lanes: cell
+// (row cn, column cul) = thread 16 cn + cul on waves 0-3. Weights stay in 32 VGPRs per lane for
+// the whole launch.
+//
+// Three exchanges lie on a step's dependency chain, W_hh1 h1 runs in a wait:
+//   poll x1 -> fc1 -> y1 (hop 1) | poll h1 -> W_hh1 h1 (while the other slots' y1 arrive)
+//   poll y1 -> fc3 -> per-slot candidate keys (hop 2)
+//   poll the 32 candidates of every row -> sample, GRU1 of step t + 1 for the slot's units ->
+//   x1, h1 (hop 3)
+// Vectors travel as 16-byte packets in MFMA B-operand order, untagged, with a sentinel-reset
+// slot pair per vector (the protocol of kernels_persist_wide_rr.hip; DESIGN.md §3.0d, the
+// buffer-ordering table of this kernel is in §3.0c). Candidates are the two-word keys of
+// cand_key.h, tagged with the step. The Gumbel noise [S][B][n] and P1 [S][B][256][4] are read
+// from the call's streams as k_persist_gen reads them: a 64-bit base per step (uniform) plus a
+// 32-bit offset inside the step.
+#include "wrnn_kernels.h"
+#include "persist_common.h"
+#include "philox.h"
+
+#include <vector>
+
+namespace wrnn {
+namespace {
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+constexpr int GH = kRH;        // rnn_dims 256
+constexpr int GF = kGF;        // fc_dims 128
+constexpr int GU = GH / kPM;   // GRU units per slot (8)
+constexpr int GO = GF / kPM;   // fc1 outputs per slot (4)
+constexpr int kRowsW = 16;     // rows per group (MFMA N)
+constexpr unsigned kSentG = 0x7fbadbadu;  // a signalling NaN: no arithmetic result is ever this
+constexpr unsigned kNoOff = 0x80000000u;  // lanes without a packet: outside every buffer
+
+// ---- exchange area per group (floats) ---------------------------------------------------
+// x1, h1 (256 units): per step parity slot [e 8][p 2][lane 64] packets of 4 floats; packet p of
+// consumer lane l = 16 c + n of wave e holds row n, units 32 e + 8 c + 4 p + q (q < 4)
+// y1 (128 units): [e 8][lane 64] packets; lane l = 16 c + n of wave e: row n, units 16 e + 4 c + q
+constexpr int GS_X = 8 * 2 * 64 * 4;
+constexpr int GS_Y = 8 * 64 * 4;
+constexpr int GX_X1 = 0, GX_H1 = GX_X1 + 2 * GS_X, GX_Y1 = GX_H1 + 2 * GS_X;
+constexpr int GX_D = GX_Y1 + 2 * GS_Y;  // candidates [row 16][slot 32] (key hi, key lo | tag)
+constexpr int GX_GROUP = GX_D + kRowsW * kPM * 2 + 64;
+static_assert(GX_GROUP % 4 == 0 && GX_D % 4 == 0, "reset works in 16-byte units");
+
+__host__ __device__ constexpr unsigned g_cons_x(int v, int l) { return (unsigned)((v * 2 * 64 + l) * 16); }
+__host__ __device__ constexpr unsigned g_cons_y(int v, int l) { return (unsigned)((v * 64 + l) * 16); }
+// packet of the unit quad u .. u + 3 (u % 4 == 0) of row cn
+__host__ __device__ constexpr unsigned g_prod_x(int u, int cn) {
+    return (unsigned)((((u >> 5) * 2 + ((u >> 2) & 1)) * 64 + 16 * ((u >> 3) & 3) + cn) * 16);
+}
+__host__ __device__ constexpr unsigned g_prod_y(int u, int cn) {
+    return (unsigned)(((u >> 4) * 64 + 16 * ((u >> 2) & 3) + cn) * 16);
+}
+// byte offset of parity slot seq & 1 of the vector at float offset `buf` (slots of `sz` floats)
+__host__ __device__ constexpr unsigned g_slot(int buf, int sz, unsigned seq) {
+    return (unsigned)buf * 4u + (seq & 1u) * (unsigned)sz * 4u;
+}
+__host__ __device__ constexpr unsigned g_cand(int n, int s) { return (unsigned)((n * kPM + s) * 2) * 4u; }
+
+// ---- LDS (floats) -------------------------------------------------------------------------
+constexpr int WL_RI = 0;         // RowInfo of the group's rows (6 words each)
+constexpr int WL_FAIL = 112;
+constexpr int WL_REG = 116;      // group, slot, registration result (ints)
+constexpr int WL_CB = 128;       // b_hh1 of the slot's units [3][8], then b_f3 of its classes @32
+constexpr int WL_P = 256;        // partial tiles [8 v][nt][16 n][16 m], one buffer per product
+constexpr int WT = 8 * 256;
+constexpr int WP_F1 = WL_P, WP_HH = WP_F1 + WT, WP_F3 = WP_HH + 2 * WT, WL_TOTAL = WP_F3 + 2 * WT;
+static_assert(sizeof(RowInfo) == 24 && kRowsW * 6 <= WL_FAIL, "RowInfo array overflows");
+static_assert(WL_CB + 32 + 32 <= WL_P, "slot constants overflow");
+
+constexpr int kWgq = 8;  // float4 weight registers per lane: T0-T2 two each, T3, T4 one each
+
+__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ float f4c(const float4& q, int i) {
+    return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w;
+}
+__device__ __forceinline__ float u4c(const u4v& q, int i) {
+    return __uint_as_float(i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w);
+}
+// conflict-free partial tiles: XOR swizzle of the 16-byte column slots by row (as
+// kernels_persist_wide_rr.hip wsw)
+__device__ __forceinline__ int wsw(int n, int o) { return ((((o >> 2) ^ (n >> 1)) & 3) << 2) | (o & 3); }
+__device__ __forceinline__ bool g_ready(const u4v& q) {
+    return (q.x != kSentG) & (q.y != kSentG) & (q.z != kSentG) & (q.w != kSentG);
+}
+__device__ __forceinline__ void gbar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Poll the lane's NP B-operand packets (1 KiB apart) until none holds the sentinel; lanes
+// without a packet (rows >= R) load from kNoOff, which reads 0. Bounded: records the first
+// timeout's site like the other wide kernels.
+template <int NP>
+__device__ __forceinline__ bool g_poll(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v (&cc)[2],
+                                       unsigned* ctl, unsigned where, unsigned step) {
+    const unsigned t0 = p_now();
+    unsigned nsp = 0;
+    while (true) {
+        unsigned vo = valid ? voff : kNoOff;
+        asm volatile("" : "+v"(vo));
+        cc[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, so, kCpNT);
+        if constexpr (NP == 2) cc[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024u, so, kCpNT);
+        bool ok = g_ready(cc[0]);
+        if constexpr (NP == 2) ok &= g_ready(cc[1]);
+        if (__all((int)ok)) return true;
+        if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
+            if ((threadIdx.x & 63) == 0 && !ld_sc1_u(ctl + PC_ERR) &&
+                atomicCAS(ctl + PC_WHERE, 0u, where | ((threadIdx.x >> 6) << 19)) == 0u) {
+                ctl[PC_WHERE + 1] = 1u;
+                ctl[PC_WHERE + 2] = step;
+            }
+            if ((threadIdx.x & 63) == 0) atomicMax(ctl + PC_ERR, 2u);
+            return false;
+        }
+    }
+}
+
+}  // namespace
+
+// DBG: the instance that records logits for the teacher-forced gate (wrnn_set_debug_steps)
+template <bool DBG>
+__global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int* sreg = reinterpret_cast<int*>(lds + WL_REG);
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int gg, ss;
+        sreg[2] = p_register(a.ctl, gg, ss);
+        sreg[0] = gg;
+        sreg[1] = ss;
+    }
+    __syncthreads();
+    if (!sreg[2]) return;
+    const int g = __builtin_amdgcn_readfirstlane(sreg[0]);
+    const int w = __builtin_amdgcn_readfirstlane(sreg[1]);
+    const int v = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave: K-eighth v of every product
+    const int l = tid & 63;
+    const int R = a.nr;
+    const int g0 = a.rb + g;
+    const int bn = l & 15;
+    const bool bvalid = bn < R;
+    const int cn = tid >> 4, cul = tid & 15;  // epilogue cell (row cn, tile row cul), waves 0-3
+    const bool cell = tid < 16 * R;
+    const bool gcell = cell && cul < GU;      // GRU cell: unit 8 w + cul
+    const bool fcell = cell && cul < GO;      // fc1 cell: output 4 w + cul
+    const int cu = GU * w + (cul & 7);
+    const int crow = g0 + kPG * (cell ? cn : 0);
+    const int ntc = a.cpw / 16;               // fc3 tiles of the slot (1 or 2)
+    const rsrc_t xr = mk_rsrc(a.xbuf + (size_t)g * GX_GROUP);
+    const unsigned o_cx = g_cons_x(v, l), o_cy = g_cons_y(v, l);
+    // publishing lanes: x1 / h1 the first lane of each unit quad, y1 the row's lane 0
+    const unsigned o_px = gcell && (cul & 3) == 0 ? g_prod_x(GU * w + cul, cn) : kNoOff;
+    const unsigned o_py = cell && cul == 0 ? g_prod_y(GO * w, cn) : kNoOff;
+    auto wh = [&](unsigned site) { return site << 28 | (unsigned)w << 22; };
+
+    // ---- weights: K = 256 tile T (< 3), k-step ks at wq[2 T + ks / 4] component ks % 4;
+    //      fc3 tile j, k-step ks at wq[6 + j] component ks -------------------------------------
+    float4 wq[kWgq];
+    {
+        const float4* src = a.wwide + ((size_t)(w * 8 + v) * kWgq) * 64 + l;
+#pragma unroll
+        for (int q = 0; q < kWgq; ++q) wq[q] = src[(size_t)q * 64];
+    }
+    if (tid < R) reinterpret_cast<RowInfo*>(lds + WL_RI)[tid] = a.rows[g0 + kPG * tid];
+    if (tid == 0) lds[WL_FAIL] = 0.f;
+    if (tid < 24) lds[WL_CB + tid] = a.b_hh1[(tid >> 3) * GH + GU * w + (tid & 7)];
+    if (tid >= 32 && tid < 32 + a.cpw) {
+        const int c = a.cpw * w + tid - 32;
+        lds[WL_CB + tid] = c < a.n_classes ? a.b_f3[c] : 0.f;
+    }
+
+    // publish the lane's value of step seq as one packet of its quad: slot seq & 1, the
+    // sentinel into slot (seq + 1) & 1. Every lane of the wave issues both stores (a lane that
+    // does not publish uses kNoOff, which the buffer range check drops): no branch around them,
+    // so the compiler's waits after them stay counted
+    auto pub = [&](int buf, int sz, unsigned off, float val, unsigned seq) {
+        const float u1 = pdpp<0x39>(val), u2 = pdpp<0x4E>(val), u3 = pdpp<0x93>(val);
+        unsigned vo = off;
+        asm volatile("" : "+v"(vo));
+        __builtin_amdgcn_raw_buffer_store_b128(
+            (u4v){__float_as_uint(val), __float_as_uint(u1), __float_as_uint(u2), __float_as_uint(u3)}, xr, vo,
+            g_slot(buf, sz, seq), 0);
+        __builtin_amdgcn_raw_buffer_store_b128((u4v){kSentG, kSentG, kSentG, kSentG}, xr, vo,
+                                               g_slot(buf, sz, seq + 1u), 0);
+    };
+    // partial tile j of a product into P ([v][nt][n][m], swizzled)
+    auto put = [&](int P, int NT, int j, const v4f& acc) {
+        *reinterpret_cast<v4f*>(lds + P + ((v * NT + j) * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc;
+    };
+    // the cell's sum of the 8 waves' partials of tile j, tile row m (fixed order v = 0 .. 7)
+    auto psum = [&](int P, int NT, int j, int m) {
+        float p[8];
+#pragma unroll
+        for (int vv = 0; vv < 8; ++vv) p[vv] = lds[P + ((vv * NT + j) * 16 + cn) * 16 + wsw(cn, m)];
+        float acc = 0.f;
+#pragma unroll
+        for (int vv = 0; vv < 8; ++vv) acc += p[vv];
+        return acc;
+    };
+
+    float h1r = 0.f, x1c = 0.f;
+    if (gcell) {  // x1, h1 of step 0 (k_persist_gen_init)
+        const float* st = a.st + (size_t)crow * 2 * GH;
+        x1c = st[cu];
+        h1r = st[GH + cu];
+    }
+    const float vr = gcell ? a.v[cu] : 0.f, vz = gcell ? a.v[GH + cu] : 0.f, vn = gcell ? a.v[2 * GH + cu] : 0.f;
+    const float w0c = gcell ? a.w0[cu] : 0.f;
+    const float* cb = lds + WL_CB;
+    const rsrc_t fcr = mk_rsrc(a.fcond);
+    // in-step byte offsets of the cell's stream operands (the step's base is uniform, 64-bit)
+    const unsigned o_p1 = (unsigned)((cell ? cn : 0) * kPG * 4 * GH + cu * 4) * 4u;
+    const unsigned o_gn = (unsigned)(crow * a.n_classes + a.cpw * w + cul) * 4u;
+    __syncthreads();
+    // initial x1, h1 (canonicalised: a signalling NaN in a carried state must not read as the
+    // sentinel), as step t0's vectors
+    if (v < 4) {
+        pub(GX_X1, GS_X, o_px, __builtin_canonicalizef(x1c), (unsigned)a.t0 + 1u);
+        pub(GX_H1, GS_X, o_px, __builtin_canonicalizef(h1r), (unsigned)a.t0 + 1u);
+    }
+    bool fail = false;
+    u4v cc[2];
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[0] = p_now();
+    for (int t = a.t0; t < a.t1; ++t) {
+        const unsigned seq = (unsigned)t + 1u;
+        // ---- per-step cell operands: fc1 conditioning of frame(t), the noise of step t, P1 of
+        // step t + 1 (clamped at the last step, where its GRU1 goes unused) ------------------
+        float pc = 0.f, pn[2] = {0.f, 0.f};
+        float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (fcell) {
+            const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[cn];
+            pc = bld(fcr, (unsigned)(p_frame(ri, t, a.hop) * a.cond_width + a.oF1 + GO * w + cul) * 4u, 0);
+        }
+        if (cell) {
+            const rsrc_t nr_ = mk_rsrc(a.gumbel + (size_t)t * a.B * a.n_classes);
+            pn[0] = bld(nr_, o_gn, 0);
+            if (ntc == 2) pn[1] = bld(nr_, o_gn + 64u, 0);
+        }
+        if (gcell) {
+            const int tn = t + 1 < a.S ? t + 1 : t;
+            pp = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                mk_rsrc(a.P1 + ((size_t)tn * a.B + g0) * 4 * GH), o_p1, 0, 0));
+        }
+        // ---- hop 1: x1 of every slot -> fc1 -> y1 -------------------------------------------
+        fail |= !g_poll<2>(xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid, cc, a.ctl, wh(1), (unsigned)t);
+        {
+            v4f acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) acc = mfma4(f4c(wq[4 + ks / 4], ks % 4), u4c(cc[ks >> 2], ks & 3), acc);
+            put(WP_F1, 1, 0, acc);
+        }
+        if (fail) lds[WL_FAIL] = 1.f;
+        gbar();
+        if (lds[WL_FAIL] != 0.f) return;
+        if (v < 4) {
+            float y = 0.f;
+            if (fcell) {
+                y = p_add(psum(WP_F1, 1, 0, cul), pc);
+                y = y > 0.f ? y : 0.f;
+            }
+            pub(GX_Y1, GS_Y, o_py, y, seq);
+        }
+        // ---- in the wait for y1: h1 of every slot -> W_hh1 h1 (GRU1 at this step's end) ------
+        fail |= !g_poll<2>(xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid, cc, a.ctl, wh(2), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const float b = u4c(cc[ks >> 2], ks & 3);
+                a0 = mfma4(f4c(wq[ks / 4], ks % 4), b, a0);
+                a1 = mfma4(f4c(wq[2 + ks / 4], ks % 4), b, a1);
+            }
+            put(WP_HH, 2, 0, a0);
+            put(WP_HH, 2, 1, a1);
+        }
+        // ---- hop 2: y1 of every slot -> fc3 -> the slot's candidate of every row ------------
+        fail |= !g_poll<1>(xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid, cc, a.ctl, wh(3), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const float b = u4c(cc[0], ks);
+                a0 = mfma4(f4c(wq[6], ks), b, a0);
+                if (ntc == 2) a1 = mfma4(f4c(wq[7], ks), b, a1);
+            }
+            put(WP_F3, 2, 0, a0);
+            if (ntc == 2) put(WP_F3, 2, 1, a1);
+        }
+        if (fail) lds[WL_FAIL] = 1.f;
+        gbar();
+        if (v < 4) {
+            const unsigned want = key_tag(seq);
+            float g1r = 0.f, g1z = 0.f, g1n = 0.f;
+            {
+                // candidate: the max key (cand_key.h cand_key, l_k + G_k formed exactly) over the
+                // slot's classes of row cn: lane cul takes classes cpw w + 16 j + cul, j < ntc
+                uint32_t kh = 0, kl = 0;
+                if (cell) {
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        if (j >= ntc) break;
+                        const int c = a.cpw * w + 16 * j + cul;
+                        const float lg = p_add(psum(WP_F3, 2, j, cul), cb[32 + 16 * j + cul]);
+                        p_dbg_logit<DBG>(a.dbg, t, crow, c, a.B, a.n_classes, lg);
+                        const CandKey k = cand_key(lg, __float_as_uint(pn[j]), c);
+                        kmax_take(kh, kl, k.hi, k.lo);
+                    }
+                }
+                row16_kmax(kh, kl);
+                unsigned vo = cell && cul == 0 ? g_cand(cn, w) : kNoOff;
+                asm volatile("" : "+v"(vo));
+                __builtin_amdgcn_raw_buffer_store_b64((u2v){kh, kl | want}, xr, vo, GX_D * 4, 0);
+            }
+            if (gcell) {  // gh1 = W_hh1 h1 + b_hh1 of the cell's unit
+                g1r = p_add(psum(WP_HH, 2, 0, cul), cb[cul]);
+                g1z = p_add(psum(WP_HH, 2, 0, 8 + cul), cb[8 + cul]);
+                g1n = p_add(psum(WP_HH, 2, 1, cul), cb[16 + cul]);
+            }
+            // ---- hop 3: sample of step t (lane cul polls slots 2 cul, 2 cul + 1 of row cn) ----
+            float x;
+            {
+                u4v q = {0u, want, 0u, want};
+                const unsigned t0s = p_now();
+                unsigned nsp = 0;
+                while (true) {
+                    if (cell) {
+                        unsigned vo = g_cand(cn, 2 * cul);
+                        asm volatile("" : "+v"(vo));
+                        q = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, GX_D * 4, kCpNT);
+                    }
+                    if (__all(((q.y & kKeyTagMask) == want) & ((q.w & kKeyTagMask) == want))) break;
+                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
+                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
+                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(4) | ((unsigned)v << 19)) == 0u) {
+                            a.ctl[PC_WHERE + 1] = 1u;
+                            a.ctl[PC_WHERE + 2] = (unsigned)t;
+                        }
+                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
+                        fail = true;
+                        break;
+                    }
+                }
+                uint32_t bh = cell ? q.x : 0u, bl = cell ? q.y : 0u;
+                kmax_take(bh, bl, cell ? q.z : 0u, cell ? q.w : 0u);
+                row16_kmax(bh, bl);  // the 32 slots' candidates: argmax over all classes of row cn
+                const int bi = key_cls(bl);
+                {
+#pragma clang fp contract(off)
+                    x = (2.0f * (float)bi) / (float)(a.n_classes - 1) - 1.0f;
+                }
+                if (w == 0 && cell && cul == 0) {
+                    int nn = cn;
+                    asm volatile("" : "+v"(nn));
+                    const unsigned ro = (unsigned)((g0 + kPG * nn) * a.ld);
+                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u,
+                                                          (unsigned)t * 2u, 0);
+                    bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
+                }
+            }
+            if (fail) lds[WL_FAIL] = 1.f;  // seen by every wave at the next step's check
+            // ---- GRU1 of step t + 1 for the slot's units -> x1, h1 ---------------------------
+            //   gi = W_ih1 (cI + w0 x) + b_ih1 = P1 + v x ; x1 = (cI + w0 x) + h1
+            float x1 = 0.f;
+            if (gcell) {
+                h1r = p_gru(fmaf(vr, x, pp.x), fmaf(vz, x, pp.y), fmaf(vn, x, pp.z), g1r, g1z, g1n, h1r);
+                x1 = p_add(fmaf(w0c, x, pp.w), h1r);
+            }
+            pub(GX_X1, GS_X, o_px, x1, seq + 1u);
+            pub(GX_H1, GS_X, o_px, h1r, seq + 1u);
+        }
+        if (w == 0 && tid == 0) {
+            if (g == 0) p_progress(a.progress, a.prog_base, t);
+            if (p_abort(a.ctl, a.progress, t)) lds[WL_FAIL] = 1.f;  // seen at the next step's check
+        }
+    }
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
+}
+
+// launch-side helpers --------------------------------------------------------------------
+// at least 96 KB so that no CU can take two workgroups of this (register-light) kernel: every
+// group must span 32 CUs
+size_t persist_wide_gen_lds_bytes() {
+    const size_t need = (size_t)WL_TOTAL * sizeof(float);
+    return need > 96 * 1024 ? need : 96 * 1024;
+}
+size_t persist_wide_gen_xbuf_floats() { return (size_t)kPG * GX_GROUP; }
+size_t persist_wide_gen_wreg_floats() { return (size_t)kPM * 8 * kWgq * 64 * 4; }
+// before every launch: the vector slots to the sentinel, the candidate area (step tags) to 0
+__global__ __launch_bounds__(256) void k_wide_gen_xbuf_reset(uint4* x) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)kPG * GX_GROUP / 4) return;
+    const unsigned f = (unsigned)((i * 4) % GX_GROUP);
+    x[i] = f >= (unsigned)GX_D ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(kSentG, kSentG, kSentG, kSentG);
+}
+hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s) {
+    const unsigned n = (unsigned)((size_t)kPG * GX_GROUP / 4);
+    k_wide_gen_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf));
+    return hipGetLastError();
+}
+int persist_wide_gen_scratch() {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, (const void*)k_persist_wide_gen<false>) != hipSuccess) return -1;
+    return (int)fa.localSizeBytes;
+}
+hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s) {
+    // whole launches of BITS rows (t0 = 0: x1, h1 of k_persist_gen_init), 512 or 1024 classes
+    // (1 or 2 fc3 tiles of 16 per slot); no rotated or time-sliced instance
+    if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || a.mode != 0 || a.t0 != 0 ||
+        a.t1 != a.S || a.vmap != nullptr || (a.n_classes != 512 && a.n_classes != 1024) ||
+        a.cpw * kPM != a.n_classes || a.wwide == nullptr)
+        return hipErrorInvalidValue;
+    const size_t lb = persist_wide_gen_lds_bytes();
+    return a.dbg.out ? persist_launch<k_persist_wide_gen<true>>(lb, a, s)
+                     : persist_launch<k_persist_wide_gen<false>>(lb, a, s);
+}
+
+// Exhaustive host check of the exchange layout (as wide_rr_layout_check): for every row count,
+// the producer packets of x1 / h1 (32 slots x R rows x 2 unit quads) and of y1 (32 slots x R
+// rows x 1 quad) coincide one to one with the consumer packets (8 waves x 64 lanes x 2 or 1
+// packets, lanes of rows >= R off) with matching (row, unit quad), inside the slot; every parity
+// slot inside its vector's area and the areas disjoint; the no-packet offset outside every
+// buffer; the candidate pairs a lane polls aligned and inside their area. Returns the violations.
+int wide_gen_layout_check(int R) {
+    if (R < 1 || R > kRowsW) return -1;
+    int bad = 0;
+    for (int kind = 0; kind < 2; ++kind) {  // 0: x1 / h1 (256 units), 1: y1 (128 units)
+        const int sz = kind ? GS_Y : GS_X, upw = kind ? GO : GU, np = kind ? 1 : 2;
+        std::vector<int> owner(sz / 4, -1);
+        int published = 0;
+        for (int w = 0; w < kPM; ++w)
+            for (int cn = 0; cn < R; ++cn)
+                for (int cul = 0; cul < upw; cul += 4) {
+                    const int u = upw * w + cul;
+                    const unsigned o = kind ? g_prod_y(u, cn) : g_prod_x(u, cn);
+                    if (o % 16 || o + 16 > (unsigned)sz * 4u) { ++bad; continue; }
+                    if (owner[o / 16] >= 0) ++bad;
+                    owner[o / 16] = u * kRowsW + cn;
+                    ++published;
+                }
+        int matched = 0;
+        for (int v = 0; v < 8; ++v)
+            for (int l = 0; l < 64; ++l) {
+                if ((l & 15) >= R) continue;
+                for (int p = 0; p < np; ++p) {
+                    const unsigned o = (kind ? g_cons_y(v, l) : g_cons_x(v, l)) + 1024u * (unsigned)p;
+                    if (o % 16 || o + 16 > (unsigned)sz * 4u) { ++bad; continue; }
+                    const int ow = owner[o / 16];
+                    if (ow < 0) { ++bad; continue; }
+                    const int want_u = kind ? 16 * v + 4 * (l >> 4) : 32 * v + 8 * (l >> 4) + 4 * p;
+                    if (ow % kRowsW != (l & 15) || ow / kRowsW != want_u) ++bad;
+                    ++matched;
+                }
+            }
+        if (matched != published) ++bad;
+    }
+    const int bufs[3] = {GX_X1, GX_H1, GX_Y1}, szs[3] = {GS_X, GS_X, GS_Y}, ends[3] = {GX_H1, GX_Y1, GX_D};
+    for (int b = 0; b < 3; ++b)
+        for (unsigned sq = 0; sq < 2; ++sq) {
+            const unsigned s0 = g_slot(bufs[b], szs[b], sq);
+            if (s0 < (unsigned)bufs[b] * 4u || s0 + (unsigned)szs[b] * 4u > (unsigned)ends[b] * 4u) ++bad;
+            if ((unsigned long long)kNoOff + s0 + 1024ull <= 0x7fffffffull) ++bad;
+        }
+    if ((unsigned long long)kNoOff + (unsigned)GX_D * 4u <= 0x7fffffffull) ++bad;
+    for (int n = 0; n < R; ++n)
+        for (int c = 0; c < 16; ++c)
+            if (g_cand(n, 2 * c) % 16 || g_cand(n, 2 * c) + 16 > (unsigned)(kRowsW * kPM * 2) * 4u ||
+                g_cand(n, 2 * c + 1) != g_cand(n, 2 * c) + 8)
+                ++bad;
+    return bad;
+}
+
+}  // namespace wrnn

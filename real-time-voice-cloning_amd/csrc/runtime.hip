@@ -135,6 +135,10 @@ struct PlanRates {
     // 16 rows per group (profiles/wide_mol/mol_wide_r*.log, least squares: tools/make_rates.py)
     double wide_mol[2] = {9.366, 0.0185};
     double wide_rr[2] = {12.0, 0.025};                     // 12.39 us at 15-16 rows (r04 wide_rr)
+    // geneing BITS on its wide kernel (kernels_persist_wide_gen.hip): base + row x r. 3.540 /
+    // 3.594 / 3.634 us at 5 / 9 / 16 rows per group (profiles/wide_gen/gen_wide_r*.log, least
+    // squares: tools/make_rates.py)
+    double wide_gen[2] = {3.508, 0.0082};
     double slice[2] = {60.0, 0.98};                        // us per extra launch, gain threshold
     // rotation: rates of the rotated instance's two bodies by rows per group (the (q + 1)-row
     // one at its single-launch rate; the q-row one the best split measured, §3.0e)
@@ -244,6 +248,7 @@ struct wrnn_handle {
         const float *wwide = nullptr, *wwide_lds = nullptr;  // wide-row launches (MFMA images)
         const float* wfc3b = nullptr;  // ... > 512 classes: the second fc3 tile (L2-streamed)
         const float* wwide_rr = nullptr;  // runtimeracer wide-row launches (kernels_persist_wide_rr.hip)
+        const float* wwide_gen = nullptr;  // geneing BITS wide-row launches (kernels_persist_wide_gen.hip)
         // sparse k_persist image (pruned checkpoints, pack_persist_sparse):
         // per-lane masks / list bases [kPM][kPT] uint4 and the block lists [kPM][kPLdsW4] float4
         bool sp_ok = false;
@@ -605,6 +610,7 @@ int pack_p1(wrnn_handle* h, bool x4) {
 
 int pack_persist_wide(wrnn_handle* h);
 int pack_persist_wide_rr(wrnn_handle* h);
+int pack_persist_wide_gen(wrnn_handle* h);
 
 int pack_persist_sparse(wrnn_handle* h);
 
@@ -1057,7 +1063,48 @@ int pack_persist_gen(wrnn_handle* h, int oF1) {
     P.b_fc3 = dv("fc3.bias");
     CHECK(rc);
     P.oF1 = oF1;
+    CHECK(pack_persist_wide_gen(h));
     P.ok = true;
+    return WRNN_OK;
+}
+
+// Geneing wide-row launch weight image (kernels_persist_wide_gen.hip): MFMA A operands. Slot w,
+// wave v, lane l (tile row m = l & 15, k-group c = l >> 4). K = 256 tiles T = 0..2, k-step ks < 8:
+// W_T[m][input 32 v + 8 c + ks] at [w][v][2 T + ks / 4][l] component ks % 4, with T0 = W_hh1 gate r
+// of unit 8 w + m (m < 8) | gate z of unit 8 w + m - 8, T1 = gate n of unit 8 w + m (m < 8) | 0,
+// T2 = fc1[:, :256] row 4 w + m (m < 4) | 0. fc3 tiles j = 0, 1 (K = 128), k-step ks < 4: fc3 row
+// cpw w + 16 j + m, input 16 v + 4 c + ks at [w][v][6 + j][l] component ks; cpw = n / 32.
+int pack_persist_wide_gen(wrnn_handle* h) {
+    auto& T = h->host;
+    auto& P = h->pw;
+    P.wwide_gen = nullptr;
+    const int H = h->H, F = h->F, A = h->A, n = h->n_classes;
+    if (h->cfg.mode != WRNN_MODE_RAW || H != kRH || F != kGF || (n != 512 && n != 1024)) return WRNN_OK;
+    const int cpw = n / kPM;
+    const auto& Whh = T["rnn1.weight_hh_l0"];
+    const auto& Wf1 = T["fc1.weight"];
+    const auto& Wf3 = T["fc3.weight"];
+    std::vector<float> wr(persist_wide_gen_wreg_floats(), 0.f);
+    const int nq = (int)(wr.size() / ((size_t)kPM * 8 * 64 * 4));  // float4 per lane (8)
+    for (int w = 0; w < kPM; ++w)
+        for (int v = 0; v < 8; ++v)
+            for (int l = 0; l < 64; ++l) {
+                const int m = l & 15, c = l >> 4;
+                float* d = wr.data() + (((size_t)w * 8 + v) * nq * 64 + l) * 4;  // + q * 256
+                for (int ks = 0; ks < 8; ++ks) {
+                    const int k = 32 * v + 8 * c + ks;
+                    const size_t at = (size_t)(ks / 4) * 256 + ks % 4;
+                    d[0 * 256 + at] = Whh[(size_t)((m < 8 ? 0 : 1) * H + 8 * w + (m & 7)) * H + k];
+                    if (m < 8) d[2 * 256 + at] = Whh[(size_t)(2 * H + 8 * w + m) * H + k];
+                    if (m < F / kPM) d[4 * 256 + at] = Wf1[(size_t)(F / kPM * w + m) * (H + A) + k];
+                }
+                for (int j = 0; j < cpw / 16; ++j)
+                    for (int ks = 0; ks < 4; ++ks)
+                        d[(6 + j) * 256 + ks] = Wf3[(size_t)(cpw * w + 16 * j + m) * F + 16 * v + 4 * c + ks];
+            }
+    int rc = WRNN_OK;
+    P.wwide_gen = upload(h, wr, &rc);
+    CHECK(rc);
     return WRNN_OK;
 }
 
@@ -2152,14 +2199,16 @@ int persist_noise(wrnn_handle* h, int S, hipStream_t st) {
         any_reg |= !L.wide;
     }
     // (a rotated plan has only register-resident launches over the same rows: any_wide false)
-    if (raw && any_wide && !any_reg) {  // every launch draws its noise in-kernel
+    // (the geneing wide kernel reads the stream like k_persist_gen: the whole stream below)
+    const bool ring_noise = any_wide && !h->pw.gen;
+    if (raw && ring_noise && !any_reg) {  // every launch draws its noise in-kernel
         CHECK(P.gumbel.alloc(sizeof(float)));
         return WRNN_OK;
     }
     CHECK(P.gumbel.alloc((size_t)S * Bp * (raw ? n : kMolNoise) * sizeof(float)));
     const uint32_t k0 = (uint32_t)(h->seed & 0xffffffffu), k1 = (uint32_t)(h->seed >> 32);
     const RowInfo* rows = (const RowInfo*)h->ws.rows.p;
-    if (raw && any_wide) {
+    if (raw && ring_noise) {
         // the wide launches draw their noise in-kernel (kernels_persist_wide.hip ring): fill
         // only the rows of the register-resident launches (C4: 16 of 144 rows, 3.6 -> 0.4 ms)
         for (const auto& L : h->p_plan)
@@ -2182,7 +2231,7 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
     const bool rr = W.rr, gen = W.gen;
     bool any_wide = false;
     for (const auto& L : h->p_plan) any_wide |= L.wide;
-    const size_t xfl = gen  ? persist_gen_xbuf_floats()
+    const size_t xfl = gen  ? std::max(persist_gen_xbuf_floats(), any_wide ? persist_wide_gen_xbuf_floats() : 0)
                        : rr ? std::max(persist_rr_xbuf_floats(), any_wide ? persist_wide_rr_xbuf_floats() : 0)
                             : std::max(persist_xbuf_floats(), any_wide ? persist_wide_xbuf_floats() : 0);
     CHECK(P.xbuf.alloc(xfl * sizeof(float)));
@@ -2277,6 +2326,7 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
         ag.k0 = (uint32_t)(h->seed & 0xffffffffu);
         ag.k1 = (uint32_t)(h->seed >> 32);
         ag.dbg = h->dbg;
+        ag.wwide = (const float4*)W.wwide_gen;
         HIPC(launch_persist_gen_init(ag, st));
     } else if (rr) {
         ar.ctl = a.ctl;
@@ -2333,7 +2383,7 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
     a.wwide = (const float4*)W.wwide;
     a.wwide_lds = (const float4*)W.wwide_lds;
     a.wfc3b = (const float4*)W.wfc3b;
-    if (any_wide) {  // the wide kernels form P1 and the noise in-kernel into this ring
+    if (any_wide && !gen) {  // the wide kernels form P1 and the noise in-kernel into this ring
         CHECK(P.wring.alloc((rr ? persist_wide_rr_ring_floats() : persist_wide_ring_floats()) * sizeof(float)));
         a.wring = P.wring.f();
         ar.wring = a.wring;
@@ -2443,7 +2493,8 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             }
         }
         if (L.wide)  // sentinel-initialised vector slots (kernels_persist_wide*.hip polls)
-            HIPC(rr ? persist_wide_rr_reset_xbuf(P.xbuf.f(), st) : persist_wide_reset_xbuf(P.xbuf.f(), st));
+            HIPC(gen  ? persist_wide_gen_reset_xbuf(P.xbuf.f(), st)
+                 : rr ? persist_wide_rr_reset_xbuf(P.xbuf.f(), st) : persist_wide_reset_xbuf(P.xbuf.f(), st));
         else
             HIPC(hipMemsetAsync(P.xbuf.p, 0, xfl * sizeof(float), st));  // step tags
         // registration words only: an error code from an earlier launch stays visible, so the
@@ -2473,7 +2524,13 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             ag.giters = a.giters;
             ag.stamps = a.stamps;
             ag.prog_base = a.prog_base;
-            le = launch_persist_gen(ag, st);
+            if (L.wide) {
+                PersistGenArgs aw = ag;
+                aw.cpw = n / kPM;  // classes per slot of the wide layout (every class owned: n = 32 cpw)
+                le = launch_persist_wide_gen(aw, st);
+            } else {
+                le = launch_persist_gen(ag, st);
+            }
         } else if (rr) {
             ar.t0 = a.t0;
             ar.t1 = a.t1;
@@ -2698,6 +2755,7 @@ static const RateKey kRateKeys[] = {
     {"wide", nullptr, nullptr, &PlanRates::wide, nullptr},
     {"wide_mol", nullptr, nullptr, nullptr, &PlanRates::wide_mol},
     {"wide_rr", nullptr, nullptr, nullptr, &PlanRates::wide_rr},
+    {"wide_gen", nullptr, nullptr, nullptr, &PlanRates::wide_gen},
     {"slice", nullptr, nullptr, nullptr, &PlanRates::slice},
     {"rot9", nullptr, &PlanRates::rot9, nullptr, nullptr},
     {"rot9_sp", nullptr, &PlanRates::rot9_sp, nullptr, nullptr},
@@ -2804,6 +2862,7 @@ struct PlanIn {
     bool c10 = false, sp = false, p1ring = false, rr_frames = false;
     bool force_sp = false;  // env WRNN_SPARSE=1: the sparse instances whatever the rates
     bool has_wide = false, has_wide_rr = false;  // (has_wide: RAW or MOL images; has_wide_rr: RAW only)
+    bool has_wide_gen = false;     // geneing BITS image (512 / 1024 classes)
     int scr[2][kPNR + 1] = {};     // fatchord k_persist [stream | ring][nr]
     int scr_sp[kPNR + 1] = {};     // sparse instances
     int scr_rot[2][kPNR + 1] = {}; // rotated instance of this topology / mode [dense | sparse][nr]
@@ -2886,6 +2945,14 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
             if (in.rr && in.has_wide_rr && in.wmode && (in.wide_scr == 0 || in.allow_wide_scratch)) {
                 if (in.wmode == 1) opts.clear();
                 for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, R.wide_rr[0] + R.wide_rr[1] * r});
+            }
+            // geneing BITS: wide launches only for calls no single register-resident launch
+            // holds (more than 32 rows), so every plan of at most 32 rows stays as it was;
+            // WRNN_PERSIST_WIDE=1 forces them at any size
+            if (in.gen && in.has_wide_gen && in.mode == WRNN_MODE_RAW && in.wmode &&
+                (in.wmode == 1 || B > kPG * kPNR) && (in.wide_scr == 0 || in.allow_wide_scratch)) {
+                if (in.wmode == 1) opts.clear();
+                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, R.wide_gen[0] + R.wide_gen[1] * r});
             }
         }
         if (in.nr_max > 0) {  // diagnostic: variant A/B (WRNN_PERSIST_NR_MAX)
@@ -3013,6 +3080,7 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
     }
     in.has_wide = in.fat && W.wwide != nullptr;
     in.has_wide_rr = W.rr && W.wwide_rr != nullptr;
+    in.has_wide_gen = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_RAW;
     if (!W.ok) return in;
     for (int c = 1; c <= kPNR; ++c) {
         if (in.fat) {
@@ -3034,6 +3102,8 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
     } else if (in.has_wide_rr) {
         in.wide_scr = persist_wide_rr_scratch();
         in.wide_rot_scr = persist_wide_rr_rot_scratch();
+    } else if (in.has_wide_gen) {
+        in.wide_scr = persist_wide_gen_scratch();
     }
     if (const char* e = std::getenv("WRNN_PERSIST_WIDE")) in.wmode = std::atoi(e);
     if (const char* e = std::getenv("WRNN_PERSIST_NR_MAX")) in.nr_max = std::atoi(e);
@@ -3675,6 +3745,12 @@ int wrnn_debug_wide_layout(int rows_per_group) {
     return bad + bad_rr;
 }
 
+int wrnn_debug_wide_gen_layout(int rows_per_group) {
+    const int bad = wide_gen_layout_check(rows_per_group);
+    if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..16");
+    return bad;
+}
+
 int wrnn_debug_wide_mol_layout(int rows_per_group) {
     const int bad = wide_mol_layout_check(rows_per_group);
     if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..16");
@@ -3763,7 +3839,8 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     in.c10 = in.n > kPM * 16;
     in.B = rows;
     in.S = seq_len;
-    // flags: 1 sparse image, 2 P1 ring / per-frame P1 (fatchord, runtimeracer), 4 wide images;
+    // flags: 1 sparse image, 2 P1 ring / per-frame P1 (fatchord, runtimeracer), 4 wide images
+    // (fatchord RAW / MOL, runtimeracer RAW, geneing BITS with 512 or 1024 classes);
     // every variant spill-free
     in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.force_sp = in.sp && (flags & 8);
@@ -3771,6 +3848,7 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     in.rr_frames = in.rr && (flags & 2);
     in.has_wide = in.fat && (flags & 4) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.has_wide_rr = in.rr && (flags & 4) && mode == WRNN_MODE_RAW;
+    in.has_wide_gen = in.gen && (flags & 4) && mode == WRNN_MODE_RAW && (in.n == 512 || in.n == 1024);
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
     PlanOut out;
     plan_call(in, R, out);

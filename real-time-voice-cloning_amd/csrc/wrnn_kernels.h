@@ -394,9 +394,21 @@ struct PersistGenArgs {
     const int2* vmap;
     const int* gnr;
     const int* giters;
+    // wide-row launches (kernels_persist_wide_gen.hip): MFMA A-operand weight image
+    const float4* wwide;    // [kPM][8 waves][8 float4][64 lanes]
 };
 
 hipError_t launch_persist_gen(const PersistGenArgs& a, hipStream_t s);
+// Wide-row geneing launch (kernels_persist_wide_gen.hip): up to kPWideRows rows per XCD group,
+// the 32 slots alike (8 GRU units, 4 fc1 outputs, n / 32 classes each), fp32 MFMA products,
+// BITS (RAW categorical) with 512 or 1024 classes.
+hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s);
+size_t persist_wide_gen_lds_bytes();
+size_t persist_wide_gen_xbuf_floats();
+size_t persist_wide_gen_wreg_floats();
+hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s);
+int persist_wide_gen_scratch();
+int wide_gen_layout_check(int rows_per_group);
 int persist_gen_rot_scratch(int nr, int mode);  // the rotated BITS / MOL instance's scratch bytes (-1: none)
 hipError_t launch_persist_gen_init(const PersistGenArgs& a, hipStream_t s);
 int persist_gen_variant_ok(int nr, int cpw, int mode);
