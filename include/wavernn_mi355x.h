@@ -139,9 +139,9 @@ int wrnn_get_stream(wrnn_handle* h, uint32_t* stream);
  * (base + i), as the reference's CPU backend seeds every worker instance explicitly
  * (vocoder/libwavernn/inference.py:106-108, :200-204). A count that does not match the
  * call's n_utts makes that call fail with WRNN_ERR_INVALID.
- * MOL: the samples are floats, and a row run by a wide MFMA launch differs in rounding from
- * the same row run by a register-resident launch (another summation order; RAW hides that
- * behind exact labels). A shard's rows equal the single-GPU call's bit for bit only when both
+ * MOL (fatchord and runtimeracer): the samples are floats, and a row run by a wide MFMA launch
+ * differs in rounding from the same row run by a register-resident launch (another summation
+ * order; RAW hides that behind exact labels). A shard's rows equal the single-GPU call's bit for bit only when both
  * calls plan the same kernel family (wrnn_plan_info); env WRNN_PERSIST_WIDE=0 keeps every MOL
  * call on the register-resident kernels and restores the strict form. */
 int wrnn_set_utt_streams(wrnn_handle* h, const uint32_t* streams, int n);
@@ -157,8 +157,9 @@ int wrnn_set_utt_streams(wrnn_handle* h, const uint32_t* streams, int n);
  * MOL: "bit for bit" holds when the piece and the whole call plan the same kernel family
  * (register-resident or wide, wrnn_plan_info): the float samples of a wide launch differ in
  * rounding from a register-resident launch's. Calls of at most 32 MOL rows stay
- * register-resident under the shipped rates; WRNN_PERSIST_WIDE=0 restores the strict form for
- * every size. */
+ * register-resident under the shipped rates (runtimeracer: under any rates, the planner offers
+ * its MOL calls wide launches only above 32 rows); WRNN_PERSIST_WIDE=0 restores the strict form
+ * for every size. */
 int wrnn_set_fold_ranges(wrnn_handle* h, const int* lo, const int* hi, int n);
 
 /* Fold arithmetic of fold_with_overlap for a mel of n_frames frames
@@ -219,7 +220,9 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap);
  * built-in defaults), every kernel variant taken as spill-free. flags: 1 sparse image, 2 P1 ring /
  * per-frame P1, 4 wide images (fatchord RAW and MOL, runtimeracer RAW, geneing BITS with 512 or
  * 1024 classes; geneing MOL / Beta have no wide launch, and geneing calls of at most 32 rows plan
- * none unless forced), 8 sparse forced (WRNN_SPARSE=1). bits outside 1..10, an unknown mode or more than 2^20 rows are
+ * none unless forced), 8 sparse forced (WRNN_SPARSE=1), 16 runtimeracer MOL wide image (flag 4
+ * does not cover it; priced by the rate key wide_rr_mol, and planned only for calls of more than
+ * 32 rows). bits outside 1..10, an unknown mode or more than 2^20 rows are
  * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag of the first `cap`,
  * and the row rotation's launch count (0: none). */
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
@@ -311,6 +314,13 @@ int wrnn_debug_wide_layout(int rows_per_group);
  * aligned inside the area, written by exactly one fc3 epilogue lane and read by exactly one
  * hop-D lane that expects that (row, logit) -- or WRNN_ERR_INVALID. No device needed. */
 int wrnn_debug_wide_mol_layout(int rows_per_group);
+/* The same for the MOL head of the runtimeracer wide launch (kernels_persist_wide_rr.hip), whose
+ * logit pairs have an area of their own after the candidates: violations among the (row, logit)
+ * pairs of a group of `rows_per_group` rows (1..16) -- each 8-byte aligned inside the area,
+ * written by exactly one fc5 epilogue lane, read in every B slot by exactly one hop-B7 lane that
+ * expects that (row, logit), disjoint from the vector slots -- or WRNN_ERR_INVALID. No device
+ * needed. */
+int wrnn_debug_wide_rr_mol_layout(int rows_per_group);
 /* The same for the geneing wide launch (kernels_persist_wide_gen.hip): violations among the x1 /
  * h1 packets (256 units), the y1 packets (128 units) and the candidate pairs of a group of
  * `rows_per_group` rows (1..16), or WRNN_ERR_INVALID. No device needed. */

@@ -53,8 +53,16 @@ constexpr int QSLOT = 8 * 2 * 64 * 4;
 constexpr int QV = 2 * QSLOT;
 enum QBuf : int { QX1 = 0, QH1, QX2, QH2, QX3, QH3, QX4, QH4, QY1, QY2, QY3, QY4, QN };
 constexpr int QX_D = QN * QV;  // candidates [row 16][B slot 16] (value, step tag << 11 | class)
-constexpr int QX_GROUP = QX_D + kRowsW * kHalf * 2 + 64;
-static_assert(QX_GROUP % 4 == 0 && QX_D % 4 == 0, "reset works in 16-byte units");
+constexpr int QX_CAND = kRowsW * kHalf * 2;
+// MOL launches publish the rows' 30 logits instead, in an area of their own after the candidates
+// (16 rows x 32 pairs are twice the candidate area): logit k of row n as a tagged pair (8 bytes:
+// float bits, step tag = the whole seq), written by cell lane k % 16 of B slot k / 16, polled by
+// lane k % 16 of row n in every B slot (wide_rr_mol_layout_check)
+constexpr int kMolLogits = 30;  // 10 mixture logits, 10 means, 10 log-scales
+constexpr int QX_L = QX_D + QX_CAND;
+constexpr int QX_LOGIT = kRowsW * 32 * 2;
+constexpr int QX_GROUP = QX_L + QX_LOGIT + 64;
+static_assert(QX_GROUP % 4 == 0 && QX_D % 4 == 0 && QX_L % 4 == 0, "reset works in 16-byte units");
 
 __host__ __device__ constexpr unsigned q_cons(int v, int l) { return (unsigned)((v * 2 * 64 + l) * 16); }
 // packet of the unit quad u .. u + 3 (u = 16 s + cul, cul % 4 == 0) of row cn
@@ -66,6 +74,10 @@ __host__ __device__ constexpr unsigned q_slot(int hb, unsigned seq) {
     return (unsigned)(hb * QV) * 4u + (seq & 1u) * (unsigned)QSLOT * 4u;
 }
 __host__ __device__ constexpr unsigned q_cand(int n, int s) { return (unsigned)((n * kHalf + s) * 2) * 4u; }
+// byte offset (inside the logit area at QX_L) of the tagged pair of logit k of row n
+__host__ __device__ constexpr unsigned q_logit(int n, int k) { return (unsigned)((n * 32 + k) * 2) * 4u; }
+static_assert(kMolLogits <= 32 && q_logit(kRowsW - 1, 31) + 8 == (unsigned)QX_LOGIT * 4u,
+              "16 rows x 32 logit pairs are exactly the logit area");
 
 // ---- per-slot operand ring (PersistRRArgs::wring): for B slot s, written by A slot s --------
 // [4 step slots][16 rows][16 units] float4 P1 (r, z, n of W_ih1 (I c) + b_ih1, then I c + b_I),
@@ -150,7 +162,15 @@ __device__ __forceinline__ bool q_poll(rsrc_t xr, unsigned voff, unsigned so, bo
 // ROT: a time-sliced launch (PersistRRArgs::vmap): row slot r of group g is the
 //      virtual row g + 8 r -> (physical row, step offset); the launch runs steps [0, t1) of its
 //      rows (their steps off .. off + t1 - 1) from the chunk state and saves it at the end
-template <bool ROT, bool DBG>
+// MOL: the mixture-of-logistics head (vocoder/distribution.py:104-140; 30 logits: fc5 is one tile
+//      of B slots 0 and 1, a zero image in the others, cpw = 16). Only half B's tail and half A's
+//      ring differ from RAW: the fc5 epilogue publishes every logit as a tagged pair (float bits,
+//      seq) into the logit area (q_logit) -- no candidate key, no noise ring (A's threads 256..
+//      idle); in hop B7 the 16 lanes of a row poll the row's 30 pairs (lane cul: logits cul and
+//      16 + cul) and form the sample with k_persist_rr<MOL>'s operations in its order, from the
+//      draws of k_mol_noise (a.gumbel [S][B][kMolNoise], lane cul < 12 holds draw cul of its row,
+//      loaded one step ahead). Every cell lane of the row then holds x.
+template <bool ROT, bool MOL, bool DBG>
 __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int* sreg = reinterpret_cast<int*>(lds + QL_REG);
@@ -185,7 +205,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
     // own cell value of a vector published by the same-numbered slot of the other half
     const unsigned o_own = cell ? o_prod + 4u * (unsigned)(cul & 3) : kNoOff;
     auto wh = [&](unsigned site) { return site << 28 | (unsigned)w << 22; };
-    const int ntc = a.cpw / 16;  // fc5 tiles of a B slot (cpw = n / 16 classes: 2 or 4)
+    const int ntc = a.cpw / 16;  // fc5 tiles of a B slot (cpw = n / 16 classes: 2 or 4; MOL: 1)
     // phase stamps of the traced step (WRNN_PHASE_STEP), wave 0 of slots 0 (A) and 16 (B)
     uint32_t* ph = a.phases != nullptr && (w == 0 || w == 16) ? a.phases + (size_t)(g * kPM + w) * kPPhases : nullptr;
 #define RS(i) \
@@ -343,7 +363,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
                 }
                 __builtin_amdgcn_raw_buffer_store_b128(
                     __builtin_bit_cast(u4v, vv), rgr, (unsigned)(((tau & 3) * kRowsW + n) * 16 + (tx & 15)) * 16u, 0, 0);
-            } else {
+            } else if constexpr (!MOL) {
                 const int i = tx - 256, n = i >> 4, jq = i & 15;
                 if (n >= R || 4 * jq >= a.cpw) return;
                 const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + QL_RI)[n];
@@ -528,7 +548,25 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
         const rsrc_t fcr = mk_rsrc(a.fcond);
         const float vr = cell ? a.v[cu] : 0.f, vz = cell ? a.v[RH + cu] : 0.f, vn = cell ? a.v[2 * RH + cu] : 0.f;
         const float w0c = cell ? a.w0[cu] : 0.f;
+        // MOL: draw cul of the cell's row at the row's absolute step te + off (clamped to the
+        // row's last step: the load of the step after the last is never used), from the
+        // k_mol_noise stream; pg is the draw of step t, pgn the one of step t + 1. One uniform
+        // base and a 32-bit lane offset (the launcher keeps the stream below 2 GiB).
+        [[maybe_unused]] float pg = 0.f, pgn = 0.f;
+        [[maybe_unused]] auto mol_draw = [&](int te) {
+            if (!cell || cul >= kMolNoise) return;
+            int nn = cn;
+            asm volatile("" : "+v"(nn));  // (recomputed per step: hoisted offsets cost registers)
+            const int off = roff(nn);
+            const int prow = ROT ? reinterpret_cast<const int2*>(lds + QL_VM)[nn].x : g0 + kPG * nn;
+            const int tc = te < a.S - off ? te : a.S - off - 1;
+            pgn = bld(mk_rsrc(a.gumbel), (unsigned)(((tc + off) * a.B + prow) * kMolNoise + cul) * 4u, 0);
+        };
         __syncthreads();
+        if constexpr (MOL) {  // the draws of step t0 (the loop loads those of t + 1 at step t)
+            mol_draw(a.t0);
+            pg = pgn;
+        }
         // initial x1, h1 (canonicalised: a signalling NaN in a carried state must not read as
         // the sentinel), as step t0's vectors
         if (v < 4) {
@@ -541,7 +579,8 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             // per-step cell operands: conditioning of frame(t) (GRU3, fc1, fc3) now; the
             // ring's noise of step t and P1 of step t + 1 (formed by the partner A slot) after
             // the x2 poll below -- A stored them before that publication
-            float pc[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, pn[4] = {0.f, 0.f, 0.f, 0.f};
+            float pc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+            [[maybe_unused]] float pn[4] = {0.f, 0.f, 0.f, 0.f};
             float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
             if (cell) {
                 const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + QL_RI)[cn];
@@ -564,12 +603,15 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             RS(3);
             const float x2v = __uint_as_float(ov);
             if (cell) {  // (non-temporal: the ring lines were written by another CU)
-                const unsigned nb = (unsigned)(RG_P + ((t & 3) * kRowsW + cn) * 64 + cul) * 4u;
+                [[maybe_unused]] const unsigned nb = (unsigned)(RG_P + ((t & 3) * kRowsW + cn) * 64 + cul) * 4u;
+                if constexpr (!MOL) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < ntc) pn[j] = bld_nt(rgr, nb + (unsigned)(16 * j) * 4u, 0);
+                    for (int j = 0; j < 4; ++j)
+                        if (j < ntc) pn[j] = bld_nt(rgr, nb + (unsigned)(16 * j) * 4u, 0);
+                }
                 pp = bld4_nt(rgr, (unsigned)((((t + 1) & 3) * kRowsW + cn) * 16 + cul) * 16u, 0);
             }
+            if constexpr (MOL) mol_draw(t + 1);
             prod(I3(), 3, cc, PB_G3);
             if (fail) lds[QL_FAIL] = 1.f;
             qbar();
@@ -644,7 +686,11 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             // ---- B6: y4 -> fc5 -> per-slot candidates ---------------------------------------
             fail |= !q_poll(xr, o_cons, q_slot(QY4, seq), bvalid, o_own_none, cc, ov, a.ctl, wh(12), (unsigned)t);
             RS(10);
-            if (ntc == 4)
+            // (MOL: one tile; B slots 2-15 run it on their zero image, so every B slot polls y4
+            // at every step as in RAW and the sentinel protocol of QY4 is unchanged)
+            if constexpr (MOL)
+                prod(I1(), 11, cc, PB_F5);
+            else if (ntc == 4)
                 prod(std::integral_constant<int, 4>(), 11, cc, PB_F5);
             else
                 prod(std::integral_constant<int, 2>(), 11, cc, PB_F5);
@@ -652,8 +698,18 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             qbar();
             RS(11);
             if (v < 4) {
-                const unsigned want = key_tag(seq);
-                {
+                [[maybe_unused]] const unsigned want = key_tag(seq);
+                if constexpr (MOL) {
+                    // MOL: logit (row cn, index cu) as a tagged pair, polled directly in hop B7
+                    // (slots 0 and 1 hold the 30 logits; the other slots publish nothing)
+                    if (cell && cu < a.n_classes) {
+                        float ps[1];
+                        psums(I1(), PB_F5, 1, 0, ps);
+                        const float lg = p_add(ps[0], cb[96 + cul]);
+                        p_dbg_logit<DBG>(a.dbg, t + roff(cn), crow, cu, a.B, a.n_classes, lg);
+                        bst_tag(lg, seq, xr, q_logit(cn, cu), QX_L * 4);
+                    }
+                } else {
                     // candidate: the max key (cand_key.h cand_key, l_k + G_k formed exactly)
                     // over the slot's classes of row cn: lane cul takes classes cpw s + 16 j + cul,
                     // j < ntc
@@ -683,7 +739,66 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
                 RS(12);
                 // ---- B7: sample of step t (lanes cul < 8 poll slots 2 cul, 2 cul + 1 of row cn)
                 float x;
-                {
+                if constexpr (MOL) {
+                    // lane (row cn, cul) polls logits cul and 16 + cul of its row (tag: the whole
+                    // seq); a lane without a logit loads from kNoOff (reads 0, not waited for)
+                    const bool ra = cell && cul < a.n_classes, rb = cell && 16 + cul < a.n_classes;
+                    unsigned va = ra ? q_logit(cn, cul) : kNoOff;
+                    unsigned vb = rb ? q_logit(cn, 16 + cul) : kNoOff;
+                    asm volatile("" : "+v"(va), "+v"(vb));
+                    u2v qa, qb;
+                    const unsigned t0s = p_now();
+                    unsigned nsp = 0;
+                    while (true) {
+                        qa = __builtin_amdgcn_raw_buffer_load_b64(xr, va, QX_L * 4, kCpNT);
+                        qb = __builtin_amdgcn_raw_buffer_load_b64(xr, vb, QX_L * 4, kCpNT);
+                        if (__all((!ra | (qa.y == seq)) & (!rb | (qb.y == seq)))) break;
+                        if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
+                            if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
+                                atomicCAS(a.ctl + PC_WHERE, 0u, wh(13) | ((unsigned)v << 19)) == 0u)
+                                a.ctl[PC_WHERE + 2] = (unsigned)t;
+                            if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
+                            fail = true;
+                            break;
+                        }
+                    }
+                    // the sample: k_persist_rr<MOL>'s operations in its order (kernels_persist_rr.hip,
+                    // "MOL:")
+                    const float la = __uint_as_float(qa.x), lb = __uint_as_float(qb.x);
+                    float bv;
+                    {
+#pragma clang fp contract(off)
+                        bv = cul < 10 ? la - pg : -INFINITY;
+                    }
+                    int bi = cul < 10 ? cul : 0x7fffffff;
+                    row16_argmax(bv, bi);  // first max over k < 10; every lane of the row gets it
+                    bi = bi < 10 ? bi : 0;
+                    const int base = l & 48;  // lane 0 of this lane's row
+                    // l[10 + bi]: the first value of lane 10 + bi, or the second of lane bi - 6
+                    const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
+                    const float mean = bi < 6 ? m0 : m1;
+                    float ls = __shfl(lb, base + 4 + bi);  // l[20 + bi]: the second value of lane 4 + bi
+                    const float lu = __shfl(pg, base + 10);
+                    {
+#pragma clang fp contract(off)
+                        const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
+                        ls = ls < lsmin ? lsmin : ls;
+                        x = mean + expf(ls) * lu;
+                        x = x < -1.f ? -1.f : x;
+                        x = x > 1.f ? 1.f : x;
+                    }
+                    pg = pgn;
+                    if (s == 0 && cell && cul == 0) {
+                        int nn = cn;
+                        asm volatile("" : "+v"(nn));
+                        unsigned ro = (unsigned)((g0 + kPG * nn) * a.ld);
+                        if (ROT) {
+                            const int2 vm = reinterpret_cast<const int2*>(lds + QL_VM)[nn];
+                            ro = (unsigned)(vm.x * a.ld + vm.y);
+                        }
+                        bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
+                    }
+                } else {
                     u4v q = {0u, want, 0u, want};
                     const unsigned t0s = p_now();
                     unsigned nsp = 0;
@@ -765,7 +880,8 @@ size_t persist_wide_rr_lds_bytes() { return (size_t)QL_TOTAL * sizeof(float); }
 size_t persist_wide_rr_xbuf_floats() { return (size_t)kPG * QX_GROUP; }
 size_t persist_wide_rr_ring_floats() { return (size_t)kPG * kHalf * RG_SLOT; }
 size_t persist_wide_rr_wreg_floats() { return (size_t)kPM * 8 * kWq * 64 * 4; }
-// before every launch: the vector slots to the sentinel, the candidate area (step tags) to 0
+// before every launch: the vector slots to the sentinel, the candidate and logit areas (step
+// tags) to 0 -- tag 0 never equals a seq >= 1
 __global__ __launch_bounds__(256) void k_wide_rr_xbuf_reset(uint4* x) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)kPG * QX_GROUP / 4) return;
@@ -777,29 +893,49 @@ hipError_t persist_wide_rr_reset_xbuf(float* xbuf, hipStream_t s) {
     k_wide_rr_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf));
     return hipGetLastError();
 }
-int persist_wide_rr_scratch() {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void*)k_persist_wide_rr<false, false>) != hipSuccess) return -1;
-    return (int)fa.localSizeBytes;
+// scratch bytes of the plain / time-sliced production instance and of its DBG twin: the larger
+int persist_wide_rr_scratch(bool mol) {
+    hipFuncAttributes fa, fd;
+    const void* f = mol ? (const void*)k_persist_wide_rr<false, true, false> : (const void*)k_persist_wide_rr<false, false, false>;
+    const void* d = mol ? (const void*)k_persist_wide_rr<false, true, true> : (const void*)k_persist_wide_rr<false, false, true>;
+    if (hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
+    if (!mol) return (int)fa.localSizeBytes;
+    if (hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
+    return (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
 }
-int persist_wide_rr_rot_scratch() {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void*)k_persist_wide_rr<true, false>) != hipSuccess) return -1;
-    return (int)fa.localSizeBytes;
+int persist_wide_rr_rot_scratch(bool mol) {
+    hipFuncAttributes fa, fd;
+    const void* f = mol ? (const void*)k_persist_wide_rr<true, true, false> : (const void*)k_persist_wide_rr<true, false, false>;
+    const void* d = mol ? (const void*)k_persist_wide_rr<true, true, true> : (const void*)k_persist_wide_rr<true, false, true>;
+    if (hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
+    if (!mol) return (int)fa.localSizeBytes;
+    if (hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
+    return (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
 }
 hipError_t launch_persist_wide_rr(const PersistRRArgs& a, hipStream_t s) {
     // full launches (t0 = 0: the initial state is built in-kernel from k_persist_rr_init's x1,
     // h1) or time-sliced ones (vmap: every row from its chunk state, t1 <= S steps, P1 formed
-    // in-kernel), RAW, 512 or 1024 classes (2 or 4 fc5 tiles of 16 per B slot)
-    if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || a.mode != 0 ||
-        a.t0 != 0 || (a.vmap ? a.t1 > a.S || a.p1q == nullptr : a.t1 != a.S) || (a.cpw != 32 && a.cpw != 64) ||
-        a.cpw * kHalf < a.n_classes || a.wwide == nullptr || a.wring == nullptr)
+    // in-kernel), RAW with 512 or 1024 classes (2 or 4 fc5 tiles of 16 per B slot) or MOL (one)
+    if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || (a.mode != 0 && a.mode != 1) ||
+        a.t0 != 0 || (a.vmap ? a.t1 > a.S || a.p1q == nullptr : a.t1 != a.S) ||
+        a.wwide == nullptr || a.wring == nullptr)
         return hipErrorInvalidValue;
     const size_t lb = persist_wide_rr_lds_bytes();
-    if (a.vmap) return a.dbg.out ? persist_launch<k_persist_wide_rr<true, true>>(lb, a, s)
-                                 : persist_launch<k_persist_wide_rr<true, false>>(lb, a, s);
-    return a.dbg.out ? persist_launch<k_persist_wide_rr<false, true>>(lb, a, s)
-                     : persist_launch<k_persist_wide_rr<false, false>>(lb, a, s);
+    if (a.mode == 1) {  // MOL
+        // 30 logits in B slots 0 and 1; the draws come from the k_mol_noise stream, indexed in 32 bits
+        if (a.cpw != 16 || a.n_classes != kMolLogits || a.gumbel == nullptr ||
+            (double)a.S * a.B * kMolNoise * 4.0 >= 2147483648.0)
+            return hipErrorInvalidValue;
+        if (a.vmap) return a.dbg.out ? persist_launch<k_persist_wide_rr<true, true, true>>(lb, a, s)
+                                     : persist_launch<k_persist_wide_rr<true, true, false>>(lb, a, s);
+        return a.dbg.out ? persist_launch<k_persist_wide_rr<false, true, true>>(lb, a, s)
+                         : persist_launch<k_persist_wide_rr<false, true, false>>(lb, a, s);
+    }
+    if ((a.cpw != 32 && a.cpw != 64) || a.cpw * kHalf < a.n_classes) return hipErrorInvalidValue;
+    if (a.vmap) return a.dbg.out ? persist_launch<k_persist_wide_rr<true, false, true>>(lb, a, s)
+                                 : persist_launch<k_persist_wide_rr<true, false, false>>(lb, a, s);
+    return a.dbg.out ? persist_launch<k_persist_wide_rr<false, false, true>>(lb, a, s)
+                     : persist_launch<k_persist_wide_rr<false, false, false>>(lb, a, s);
 }
 
 // Exhaustive host check of the exchange layout (as wide_layout_check for the fatchord kernel):
@@ -852,7 +988,57 @@ int wide_rr_layout_check(int R) {
                 ++bad;
     for (int n = 0; n < R; ++n)
         for (int s = 0; s < kHalf; s += 2)
-            if (q_cand(n, s) % 16 || q_cand(n, s) + 16 > (unsigned)(kRowsW * kHalf * 2) * 4u) ++bad;
+            if (q_cand(n, s) % 16 || q_cand(n, s) + 16 > (unsigned)QX_CAND * 4u) ++bad;
+    return bad;
+}
+
+// Host check of the MOL logit pairs (q_logit) for a group of R rows: every (row, logit) pair is
+// 8-byte aligned inside the logit area, written by exactly one (B slot, cell lane) of the fc5
+// epilogue (slot s, lane cul: logit 16 s + cul < 30) and read, in every B slot, by exactly one
+// hop-B7 lane of the row (lane cul: logits cul and 16 + cul) that expects that (row, logit); no
+// two pairs overlap; the area lies after the vector slots and the candidates, inside the group's
+// exchange area, in the part the reset zeroes; the no-logit offset fails the range check.
+// Returns the violations.
+int wide_rr_mol_layout_check(int R) {
+    if (R < 1 || R > kRowsW) return -1;
+    int bad = 0;
+    const int np = QX_LOGIT / 2;
+    std::vector<int> wr(np, 0), id(np, -1);
+    for (int s = 0; s < kHalf; ++s)
+        for (int cn = 0; cn < R; ++cn)
+            for (int cul = 0; cul < 16; ++cul) {
+                const int k = 16 * s + cul;
+                if (k >= kMolLogits) continue;  // (the epilogue's `cu < n_classes`)
+                const unsigned o = q_logit(cn, k);
+                if (o % 8 || o + 8 > (unsigned)QX_LOGIT * 4u) { ++bad; continue; }
+                ++wr[o / 8];
+                id[o / 8] = cn * 32 + k;
+            }
+    for (int s = 0; s < kHalf; ++s) {  // the readers of B slot s
+        std::vector<int> rd(np, 0);
+        for (int cn = 0; cn < R; ++cn)
+            for (int cul = 0; cul < 16; ++cul)
+                for (int k = cul; k < kMolLogits; k += 16) {
+                    const unsigned o = q_logit(cn, k);
+                    if (o % 8 || o + 8 > (unsigned)QX_LOGIT * 4u) { ++bad; continue; }
+                    ++rd[o / 8];
+                    if (id[o / 8] != cn * 32 + k) ++bad;  // the reader expects another (row, logit)
+                }
+        for (int i = 0; i < np; ++i)
+            if (rd[i] > 1 || rd[i] != wr[i]) ++bad;
+    }
+    int pairs = 0;
+    for (int i = 0; i < np; ++i) {
+        if (wr[i] > 1) ++bad;
+        pairs += wr[i];
+    }
+    if (pairs != R * kMolLogits) ++bad;
+    // disjoint from the vector slots and the candidates, inside the group's area
+    for (int hb = 0; hb < QN; ++hb)
+        for (unsigned sq = 0; sq < 2; ++sq)
+            if (q_slot(hb, sq) + (unsigned)QSLOT * 4u > (unsigned)QX_L * 4u) ++bad;
+    if (QX_D + QX_CAND > QX_L || QX_L + QX_LOGIT > QX_GROUP || QX_L < QX_D || QX_L % 2) ++bad;
+    if ((unsigned long long)kNoOff + (unsigned long long)QX_L * 4ull + 8ull <= 0x7fffffffull) ++bad;
     return bad;
 }
 

@@ -135,6 +135,10 @@ struct PlanRates {
     // 16 rows per group (profiles/wide_mol/mol_wide_r*.log, least squares: tools/make_rates.py)
     double wide_mol[2] = {9.366, 0.0185};
     double wide_rr[2] = {12.0, 0.025};                     // 12.39 us at 15-16 rows (r04 wide_rr)
+    // the MOL head on the runtimeracer wide kernel: base + row x r. 9.43 / 9.60 / 9.79 us at 5 / 9 /
+    // 16 rows per group (profiles/wide_rr_mol/rr_mol_wide_r*.log, least squares:
+    // tools/make_rates.py)
+    double wide_rr_mol[2] = {9.285, 0.0321};
     // geneing BITS on its wide kernel (kernels_persist_wide_gen.hip): base + row x r. 3.540 /
     // 3.594 / 3.634 us at 5 / 9 / 16 rows per group (profiles/wide_gen/gen_wide_r*.log, least
     // squares: tools/make_rates.py)
@@ -968,13 +972,17 @@ int pack_persist_rr(wrnn_handle* h, int oG3, int oF1, int oF3) {
 // at [w][v][2 T + ks / 4][l] component ks % 4. Tiles of A: W_ih2 r, z, n | W_hh2 r, z, n | W_ih4
 // r, z, n | W_hh4 r, z, n | fc2 | fc4; of B: W_hh1 r, z, n | W_ih3[:, :256] r, z, n | W_hh3 r, z,
 // n | fc1[:, :256] | fc3[:, :256] | fc5 rows cpw s + 16 j + m (j < n / 256), cpw = n / 16.
+// MOL (30 logits): cpw = 16, so fc5 is tile 11 alone, rows 16 s + m < 30 in B slots 0 and 1 and
+// zeros in every other slot.
 int pack_persist_wide_rr(wrnn_handle* h) {
     auto& T = h->host;
     auto& P = h->pw;
     P.wwide_rr = nullptr;
     const int H = h->H, F = h->F, A = h->A, n = h->n_classes;
-    if (h->cfg.mode != WRNN_MODE_RAW || H != kRH || F != kRH || (n != 512 && n != 1024)) return WRNN_OK;
-    const int cpw = n / 16;
+    const bool mol = h->cfg.mode == WRNN_MODE_MOL;
+    if (H != kRH || F != kRH) return WRNN_OK;
+    if (mol ? n != 30 : h->cfg.mode != WRNN_MODE_RAW || (n != 512 && n != 1024)) return WRNN_OK;
+    const int cpw = mol ? 16 : n / 16;
     auto g3 = [&](const char* key, int ld, int t, int u, int k) { return T[key][(size_t)(t * H + u) * ld + k]; };
     auto elem = [&](int w, int tile, int m, int k) -> float {
         const int s = w & 15, u = 16 * s + m;
@@ -2544,7 +2552,8 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             ar.prog_base = a.prog_base;
             if (L.wide) {
                 PersistRRArgs aw = ar;
-                aw.cpw = n / 16;  // classes per B slot of the wide layout (16 slots per half)
+                // classes per B slot of the wide layout (16 slots per half; MOL: one tile of 16)
+                aw.cpw = a.mode == WRNN_MODE_MOL ? 16 : n / 16;
                 le = launch_persist_wide_rr(aw, st);
             } else {
                 le = launch_persist_rr(ar, st);
@@ -2755,6 +2764,7 @@ static const RateKey kRateKeys[] = {
     {"wide", nullptr, nullptr, &PlanRates::wide, nullptr},
     {"wide_mol", nullptr, nullptr, nullptr, &PlanRates::wide_mol},
     {"wide_rr", nullptr, nullptr, nullptr, &PlanRates::wide_rr},
+    {"wide_rr_mol", nullptr, nullptr, nullptr, &PlanRates::wide_rr_mol},
     {"wide_gen", nullptr, nullptr, nullptr, &PlanRates::wide_gen},
     {"slice", nullptr, nullptr, nullptr, &PlanRates::slice},
     {"rot9", nullptr, &PlanRates::rot9, nullptr, nullptr},
@@ -2862,6 +2872,7 @@ struct PlanIn {
     bool c10 = false, sp = false, p1ring = false, rr_frames = false;
     bool force_sp = false;  // env WRNN_SPARSE=1: the sparse instances whatever the rates
     bool has_wide = false, has_wide_rr = false;  // (has_wide: RAW or MOL images; has_wide_rr: RAW only)
+    bool has_wide_rr_mol = false;  // runtimeracer MOL image (30 logits)
     bool has_wide_gen = false;     // geneing BITS image (512 / 1024 classes)
     int scr[2][kPNR + 1] = {};     // fatchord k_persist [stream | ring][nr]
     int scr_sp[kPNR + 1] = {};     // sparse instances
@@ -2894,9 +2905,18 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
     auto wide_us = [&](int r) {
         return mol ? R.wide_mol[0] + R.wide_mol[1] * r : R.wide[0] + R.wide[1] * r + (in.c10 ? R.wide[2] : 0.0);
     };
+    // ... and of a runtimeracer one
+    auto wide_rr_us = [&](int r) {
+        return mol ? R.wide_rr_mol[0] + R.wide_rr_mol[1] * r : R.wide_rr[0] + R.wide_rr[1] * r;
+    };
     // a wide MOL launch indexes the k_mol_noise stream ([S][rows][kMolNoise], rows padded to a
-    // launch) in 32 bits: it must stay below 2 GiB (launch_persist_wide refuses it otherwise)
+    // launch) in 32 bits: it must stay below 2 GiB (launch_persist_wide and
+    // launch_persist_wide_rr refuse it otherwise)
     const bool wide_fits = !mol || (double)S * (B + kPG * kPWideRows) * kMolNoise * 4.0 < 2147483648.0;
+    // runtimeracer MOL: wide launches only for calls no single register-resident launch holds
+    // (more than 32 rows), so every plan of at most 32 rows stays as it was; WRNN_PERSIST_WIDE=1
+    // forces them at any size (as geneing below)
+    const bool rr_mol_wide = in.rr && in.has_wide_rr_mol && mol && wide_fits && (in.wmode == 1 || B > kPG * kPNR);
     struct Opt {
         int nr;
         bool wide;
@@ -2942,9 +2962,10 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
         } else {
             for (int r = 1; r <= kPNR; ++r)
                 if (in.ok_reg[r]) opts.push_back({r, false, in.gen ? R.gen[r] : R.rr[r]});
-            if (in.rr && in.has_wide_rr && in.wmode && (in.wide_scr == 0 || in.allow_wide_scratch)) {
+            if (in.rr && ((in.has_wide_rr && in.mode == WRNN_MODE_RAW) || rr_mol_wide) && in.wmode &&
+                (in.wide_scr == 0 || in.allow_wide_scratch)) {
                 if (in.wmode == 1) opts.clear();
-                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, R.wide_rr[0] + R.wide_rr[1] * r});
+                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, wide_rr_us(r)});
             }
             // geneing BITS: wide launches only for calls no single register-resident launch
             // holds (more than 32 rows), so every plan of at most 32 rows stays as it was;
@@ -2986,16 +3007,17 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
         }
     }
     // time-sliced wide launches, when cheaper than the plan above by the same rates (P1 formed
-    // in-kernel: fatchord RAW up to 1024 classes and MOL, runtimeracer RAW)
+    // in-kernel: fatchord RAW up to 1024 classes and MOL, runtimeracer RAW and MOL)
     const bool fat_sl = in.ok && in.fat && in.has_wide && in.p1ring && wide_fits &&
                         (in.mode == WRNN_MODE_RAW || mol);
-    const bool rr_sl = in.ok && in.rr && in.has_wide_rr && in.rr_frames && in.mode == WRNN_MODE_RAW;
+    const bool rr_sl = in.ok && in.rr && in.rr_frames &&
+                       ((in.has_wide_rr && in.mode == WRNN_MODE_RAW) || rr_mol_wide);
     if ((fat_sl || rr_sl) && !out.lplan.empty() && !in.slice_off && in.wmode && in.wide_rot_scr == 0) {
         std::vector<wrnn_handle::WLaunch> sl;
         if (plan_wide_slices(B, S, sl)) {
             double cost = R.slice[0] * (sl.size() - 1);  // (an extra launch: weights, ring prologue)
             for (const auto& L : sl)
-                cost += L.steps * (fat_sl ? wide_us(L.nr) : R.wide_rr[0] + R.wide_rr[1] * L.nr);
+                cost += L.steps * (fat_sl ? wide_us(L.nr) : wide_rr_us(L.nr));
             if (cost < R.slice[1] * out.plan_us * S) {
                 out.lplan.clear();
                 for (int j = 0; j < (int)sl.size(); ++j) out.lplan.push_back({0, sl[j].nr, true, j});
@@ -3079,7 +3101,8 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
         if (!std::strcmp(e, "1")) in.force_sp = true;
     }
     in.has_wide = in.fat && W.wwide != nullptr;
-    in.has_wide_rr = W.rr && W.wwide_rr != nullptr;
+    in.has_wide_rr = W.rr && W.wwide_rr != nullptr && in.mode == WRNN_MODE_RAW;
+    in.has_wide_rr_mol = W.rr && W.wwide_rr != nullptr && in.mode == WRNN_MODE_MOL;
     in.has_wide_gen = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_RAW;
     if (!W.ok) return in;
     for (int c = 1; c <= kPNR; ++c) {
@@ -3099,9 +3122,9 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
     if (in.has_wide) {
         in.wide_scr = persist_wide_scratch(in.c10, in.mode == WRNN_MODE_MOL);
         in.wide_rot_scr = persist_wide_rot_scratch(in.c10, in.mode == WRNN_MODE_MOL);
-    } else if (in.has_wide_rr) {
-        in.wide_scr = persist_wide_rr_scratch();
-        in.wide_rot_scr = persist_wide_rr_rot_scratch();
+    } else if (in.has_wide_rr || in.has_wide_rr_mol) {
+        in.wide_scr = persist_wide_rr_scratch(in.has_wide_rr_mol);
+        in.wide_rot_scr = persist_wide_rr_rot_scratch(in.has_wide_rr_mol);
     } else if (in.has_wide_gen) {
         in.wide_scr = persist_wide_gen_scratch();
     }
@@ -3757,6 +3780,12 @@ int wrnn_debug_wide_mol_layout(int rows_per_group) {
     return bad;
 }
 
+int wrnn_debug_wide_rr_mol_layout(int rows_per_group) {
+    const int bad = wide_rr_mol_layout_check(rows_per_group);
+    if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..16");
+    return bad;
+}
+
 int wrnn_debug_beta(uint64_t seed, uint32_t stream, uint32_t step, uint32_t row, float alpha,
                     float beta, float* out) {
     if (!out) return fail(WRNN_ERR_INVALID, "null argument");
@@ -3840,14 +3869,15 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     in.B = rows;
     in.S = seq_len;
     // flags: 1 sparse image, 2 P1 ring / per-frame P1 (fatchord, runtimeracer), 4 wide images
-    // (fatchord RAW / MOL, runtimeracer RAW, geneing BITS with 512 or 1024 classes);
-    // every variant spill-free
+    // (fatchord RAW / MOL, runtimeracer RAW, geneing BITS with 512 or 1024 classes), 16 the
+    // runtimeracer MOL wide image; every variant spill-free
     in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.force_sp = in.sp && (flags & 8);
     in.p1ring = in.fat && (flags & 2);
     in.rr_frames = in.rr && (flags & 2);
     in.has_wide = in.fat && (flags & 4) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.has_wide_rr = in.rr && (flags & 4) && mode == WRNN_MODE_RAW;
+    in.has_wide_rr_mol = in.rr && (flags & 16) && mode == WRNN_MODE_MOL;
     in.has_wide_gen = in.gen && (flags & 4) && mode == WRNN_MODE_RAW && (in.n == 512 || in.n == 1024);
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
     PlanOut out;

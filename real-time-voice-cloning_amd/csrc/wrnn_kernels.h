@@ -344,16 +344,18 @@ hipError_t launch_persist_rr(const PersistRRArgs& a, hipStream_t s);
 int persist_rr_rot_scratch(int nr, bool mol);  // the rotated RAW / MOL instance's scratch bytes (-1: none)
 // Wide-row runtimeracer launch (kernels_persist_wide_rr.hip): up to kPWideRows rows per XCD
 // group, the group split into two halves of 16 slots that own 16 units of alternate layers,
-// fp32 MFMA products, RAW categorical with 512 or 1024 classes (cpw = n / 16 per B slot).
+// fp32 MFMA products, RAW categorical with 512 or 1024 classes (cpw = n / 16 per B slot) or the
+// mixture-of-logistics head (30 logits, cpw = 16: one fc5 tile in B slots 0 and 1).
 hipError_t launch_persist_wide_rr(const PersistRRArgs& a, hipStream_t s);
 size_t persist_wide_rr_lds_bytes();
 size_t persist_wide_rr_xbuf_floats();
 size_t persist_wide_rr_ring_floats();
 size_t persist_wide_rr_wreg_floats();
 hipError_t persist_wide_rr_reset_xbuf(float* xbuf, hipStream_t s);
-int persist_wide_rr_scratch();
-int persist_wide_rr_rot_scratch();  // the time-sliced instance (PersistRRArgs::vmap)
+int persist_wide_rr_scratch(bool mol = false);
+int persist_wide_rr_rot_scratch(bool mol = false);  // the time-sliced instance (PersistRRArgs::vmap)
 int wide_rr_layout_check(int rows_per_group);
+int wide_rr_mol_layout_check(int rows_per_group);  // host: violations of the MOL logit-pair layout
 
 // ---------------------------------------------------------------------------------------
 // Persistent geneing recurrence (kernels_persist_gen.hip): rnn_dims 256, fc_dims 128; per
