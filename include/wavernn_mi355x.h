@@ -139,11 +139,13 @@ int wrnn_get_stream(wrnn_handle* h, uint32_t* stream);
  * (base + i), as the reference's CPU backend seeds every worker instance explicitly
  * (vocoder/libwavernn/inference.py:106-108, :200-204). A count that does not match the
  * call's n_utts makes that call fail with WRNN_ERR_INVALID.
- * MOL (fatchord and runtimeracer): the samples are floats, and a row run by a wide MFMA launch
- * differs in rounding from the same row run by a register-resident launch (another summation
- * order; RAW hides that behind exact labels). A shard's rows equal the single-GPU call's bit for bit only when both
- * calls plan the same kernel family (wrnn_plan_info); env WRNN_PERSIST_WIDE=0 keeps every MOL
- * call on the register-resident kernels and restores the strict form. */
+ * MOL (every topology) and the geneing Beta head ('RAW'): the samples are floats, and a row run
+ * by a wide MFMA launch differs in rounding from the same row run by a register-resident launch
+ * (another summation order; RAW hides that behind exact labels). A shard's rows equal the
+ * single-GPU call's bit for bit only when both calls plan the same kernel family
+ * (wrnn_plan_info). Geneing and runtimeracer calls of at most 32 rows stay register-resident
+ * whatever the rates; env WRNN_PERSIST_WIDE=0 keeps every MOL / Beta call on the
+ * register-resident kernels and restores the strict form. */
 int wrnn_set_utt_streams(wrnn_handle* h, const uint32_t* streams, int n);
 /* Fold range of each utterance of the NEXT wrnn_generate_batch_device call only (n = its
  * n_utts; n = 0 clears): utterance u runs only its fold rows lo[u] .. hi[u] - 1 (0 <= lo < hi
@@ -157,9 +159,10 @@ int wrnn_set_utt_streams(wrnn_handle* h, const uint32_t* streams, int n);
  * MOL: "bit for bit" holds when the piece and the whole call plan the same kernel family
  * (register-resident or wide, wrnn_plan_info): the float samples of a wide launch differ in
  * rounding from a register-resident launch's. Calls of at most 32 MOL rows stay
- * register-resident under the shipped rates (runtimeracer: under any rates, the planner offers
- * its MOL calls wide launches only above 32 rows); WRNN_PERSIST_WIDE=0 restores the strict form
- * for every size. */
+ * register-resident under the shipped rates (runtimeracer and geneing: under any rates, the
+ * planner offers their MOL calls wide launches only above 32 rows); the same holds for the
+ * geneing Beta head ('RAW'), whose wide launch rounds its two logits differently from
+ * k_persist_gen. WRNN_PERSIST_WIDE=0 restores the strict form for every size. */
 int wrnn_set_fold_ranges(wrnn_handle* h, const int* lo, const int* hi, int n);
 
 /* Fold arithmetic of fold_with_overlap for a mel of n_frames frames
@@ -219,10 +222,11 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap);
  * `seq_len` steps of a model_type / bits / mode model under the rate table `table` (NULL: the
  * built-in defaults), every kernel variant taken as spill-free. flags: 1 sparse image, 2 P1 ring /
  * per-frame P1, 4 wide images (fatchord RAW and MOL, runtimeracer RAW, geneing BITS with 512 or
- * 1024 classes; geneing MOL / Beta have no wide launch, and geneing calls of at most 32 rows plan
- * none unless forced), 8 sparse forced (WRNN_SPARSE=1), 16 runtimeracer MOL wide image (flag 4
+ * 1024 classes; flag 4 does not cover geneing MOL / Beta, and geneing calls of at most 32 rows
+ * plan none unless forced), 8 sparse forced (WRNN_SPARSE=1), 16 runtimeracer MOL wide image (flag 4
  * does not cover it; priced by the rate key wide_rr_mol, and planned only for calls of more than
- * 32 rows). bits outside 1..10, an unknown mode or more than 2^20 rows are
+ * 32 rows), 32 geneing MOL wide image, 64 geneing Beta wide image (rate keys wide_gen_mol /
+ * wide_gen_beta, likewise only for calls of more than 32 rows). bits outside 1..10, an unknown mode or more than 2^20 rows are
  * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag of the first `cap`,
  * and the row rotation's launch count (0: none). */
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
@@ -325,6 +329,13 @@ int wrnn_debug_wide_rr_mol_layout(int rows_per_group);
  * h1 packets (256 units), the y1 packets (128 units) and the candidate pairs of a group of
  * `rows_per_group` rows (1..16), or WRNN_ERR_INVALID. No device needed. */
 int wrnn_debug_wide_gen_layout(int rows_per_group);
+/* The continuous heads of the geneing wide launch (MOL: n_logits 30, Beta: 2), whose logits
+ * travel as tagged pairs in the candidate area: violations among the (row, logit) pairs of a group
+ * of `rows_per_group` rows (1..16) -- each 8-byte aligned inside the area, written by exactly one
+ * fc3 epilogue lane of exactly one slot, read in every slot by exactly one hop-3 lane that expects
+ * that (row, logit), the area disjoint from the vector slots -- or WRNN_ERR_INVALID (also for any
+ * other n_logits). No device needed. */
+int wrnn_debug_wide_gen_mol_layout(int rows_per_group, int n_logits);
 
 /* Raw access for tests: copy the RAW noise (seq_len, rows, n_classes) of the last call's
  * first `n_steps` steps to host (float32). */

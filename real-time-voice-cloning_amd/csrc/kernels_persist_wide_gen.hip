@@ -1,7 +1,9 @@
 // Persistent geneing recurrence for WIDE row batches (launch kind "persist-wide" of the geneing
 // topology): up to 16 fold rows per XCD group, 128 rows per launch, every product on the fp32
-// matrix cores (v_mfma_f32_16x16x4_f32). geneing 'BITS' (WRNN_MODE_RAW), 512 or 1024 classes;
-// MOL and Beta stay on k_persist_gen.
+// matrix cores (v_mfma_f32_16x16x4_f32). Three heads, each its own instantiation (template
+// parameter MODE): geneing 'BITS' (WRNN_MODE_RAW, 512 or 1024 classes), MOL (30 logits, mixture of
+// logistics) and Beta (geneing 'RAW', WRNN_MODE_BETA, 2 logits). Calls of at most 32 rows stay on
+// k_persist_gen (the planner offers this kernel above that, or under WRNN_PERSIST_WIDE=1).
 //
 // Reference step body: vocoder/models/geneing_version.py:193-205 (rnn_dims 256, fc_dims 128):
 //   x1 = I(x0) + h1'     h1' = rnn1(I(x0), h1)
@@ -35,6 +37,25 @@
 // cand_key.h, tagged with the step. The Gumbel noise [S][B][n] and P1 [S][B][256][4] are read
 // from the call's streams as k_persist_gen reads them: a 64-bit base per step (uniform) plus a
 // 32-bit offset inside the step.
+//
+// MOL / Beta (MODE 1 / 2): fc3 has 30 / 2 outputs, so it is one 16-row tile per slot (cpw = 16):
+// slots 0 and 1 hold logit rows 16 w + m (Beta: slot 0 rows 0 and 1), every other slot runs the
+// tile on a zero image, so all 32 slots still poll x1, h1 and y1 and the sentinel protocol of the
+// vectors is exactly BITS's. No Gumbel stream is read and no candidate is formed: the fc3
+// epilogue of the owning slots publishes each (row, logit) as a tagged pair (float bits, the whole
+// step tag seq = t + 1) into the candidate area, which has exactly the shape [16 rows][32] pairs
+// and is zeroed before every launch (g_logit; wide_gen_mol_layout_check). In hop 3 lane cul of a
+// row polls logits cul and 16 + cul of its row, bounded like every other spin, and every slot
+// forms the sample redundantly (each needs x for its own GRU units); slot 0 writes `samples`,
+// there are no labels. The area is single-buffered like the candidates: a slot publishes the
+// logits of step t + 1 only after y1 of t + 1 of every slot, which follows x1 of t + 1 of every
+// slot, which every slot publishes after its hop 3 of step t.
+//   MOL:  k_persist_gen's operations in its order (first max over the 10 mixture logits minus
+//         their draws, mean, log-scale clamp, mean + exp(ls) lu, clamp to [-1, 1]); the 11 draws of
+//         a row come from the k_mol_noise stream [S][B][kMolNoise], lane cul holds draw cul,
+//         loaded one step ahead.
+//   Beta: lanes 0 and 1 of a row draw X ~ Gamma(exp l0), Y ~ Gamma(exp l1) concurrently (philox.h
+//         gamma_mt, keyed by the row's step, fold and stream), lane 0 forms 2 X / (X + Y) - 1.
 #include "wrnn_kernels.h"
 #include "persist_common.h"
 #include "philox.h"
@@ -78,6 +99,13 @@ __host__ __device__ constexpr unsigned g_slot(int buf, int sz, unsigned seq) {
     return (unsigned)buf * 4u + (seq & 1u) * (unsigned)sz * 4u;
 }
 __host__ __device__ constexpr unsigned g_cand(int n, int s) { return (unsigned)((n * kPM + s) * 2) * 4u; }
+// MOL / BETA launches publish no candidate: the area holds the rows' logits instead, logit k
+// (< 30 or 2) of row n as a tagged pair (float bits, the whole step tag seq = t + 1) at the
+// place of the candidate of "slot" k; byte offset inside the area (wide_gen_mol_layout_check)
+constexpr int kGenLogitsMax = 32;
+__host__ __device__ constexpr unsigned g_logit(int n, int k) { return (unsigned)((n * kGenLogitsMax + k) * 2) * 4u; }
+static_assert(kGenLogitsMax == kPM && g_logit(kRowsW - 1, kGenLogitsMax - 1) + 8 == (unsigned)(kRowsW * kPM * 2) * 4u,
+              "the logit pairs fill the candidate area");
 
 // ---- LDS (floats) -------------------------------------------------------------------------
 constexpr int WL_RI = 0;         // RowInfo of the group's rows (6 words each)
@@ -139,9 +167,12 @@ __device__ __forceinline__ bool g_poll(rsrc_t xr, unsigned voff, unsigned so, bo
 
 }  // namespace
 
+// MODE: 0 BITS (categorical), 1 MOL, 2 BETA (geneing 'RAW'); each its own instantiation (the BETA
+//       float64 gamma sampler would otherwise raise the other instances' register allocation)
 // DBG: the instance that records logits for the teacher-forced gate (wrnn_set_debug_steps)
-template <bool DBG>
+template <int MODE, bool DBG>
 __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
+    static_assert(MODE >= 0 && MODE <= 2, "BITS, MOL or BETA");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int* sreg = reinterpret_cast<int*>(lds + WL_REG);
     const int tid = threadIdx.x;
@@ -167,7 +198,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
     const bool fcell = cell && cul < GO;      // fc1 cell: output 4 w + cul
     const int cu = GU * w + (cul & 7);
     const int crow = g0 + kPG * (cell ? cn : 0);
-    const int ntc = a.cpw / 16;               // fc3 tiles of the slot (1 or 2)
+    const int ntc = MODE == 0 ? a.cpw / 16 : 1;  // fc3 tiles of the slot (1 or 2; MOL / BETA: 1)
     const rsrc_t xr = mk_rsrc(a.xbuf + (size_t)g * GX_GROUP);
     const unsigned o_cx = g_cons_x(v, l), o_cy = g_cons_y(v, l);
     // publishing lanes: x1 / h1 the first lane of each unit quad, y1 the row's lane 0
@@ -232,8 +263,26 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
     const rsrc_t fcr = mk_rsrc(a.fcond);
     // in-step byte offsets of the cell's stream operands (the step's base is uniform, 64-bit)
     const unsigned o_p1 = (unsigned)((cell ? cn : 0) * kPG * 4 * GH + cu * 4) * 4u;
-    const unsigned o_gn = (unsigned)(crow * a.n_classes + a.cpw * w + cul) * 4u;
+    const unsigned o_gn = MODE == 1 ? (unsigned)(crow * kMolNoise + cul) * 4u
+                                    : (unsigned)(crow * a.n_classes + a.cpw * w + cul) * 4u;
+    // MOL: lane cul < kMolNoise of a row holds draw cul of its row from the k_mol_noise stream
+    // ([S][B][kMolNoise]); pg is the draw of step t, pgn the one of step t + 1 (clamped at the
+    // last step, where it goes unused)
+    [[maybe_unused]] float pg = 0.f, pgn = 0.f;
+    [[maybe_unused]] auto mol_draw = [&](int te) {
+        const int tc = te < a.S ? te : a.S - 1;
+        if (cell && cul < kMolNoise) pgn = bld(mk_rsrc(a.gumbel + (size_t)tc * a.B * kMolNoise), o_gn, 0);
+    };
+    // MOL / BETA: the lane's pair in the logit area as producer (slots 0 and 1: logit 16 w + cul)
+    // and as consumer (logits cul and 16 + cul of row cn); kNoOff where there is none
+    [[maybe_unused]] const bool l_ra = cell && cul < a.n_classes, l_rb = cell && 16 + cul < a.n_classes;
+    [[maybe_unused]] const unsigned o_lp =
+        cell && w < 2 && 16 * w + cul < a.n_classes ? g_logit(cn, 16 * w + cul) : kNoOff;
     __syncthreads();
+    if constexpr (MODE == 1) {  // the draws of step t0 (the loop loads those of t + 1 at step t)
+        mol_draw(a.t0);
+        pg = pgn;
+    }
     // initial x1, h1 (canonicalised: a signalling NaN in a carried state must not read as the
     // sentinel), as step t0's vectors
     if (v < 4) {
@@ -247,16 +296,21 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
         const unsigned seq = (unsigned)t + 1u;
         // ---- per-step cell operands: fc1 conditioning of frame(t), the noise of step t, P1 of
         // step t + 1 (clamped at the last step, where its GRU1 goes unused) ------------------
-        float pc = 0.f, pn[2] = {0.f, 0.f};
+        float pc = 0.f;
+        [[maybe_unused]] float pn[2] = {0.f, 0.f};
         float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
         if (fcell) {
             const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[cn];
             pc = bld(fcr, (unsigned)(p_frame(ri, t, a.hop) * a.cond_width + a.oF1 + GO * w + cul) * 4u, 0);
         }
-        if (cell) {
-            const rsrc_t nr_ = mk_rsrc(a.gumbel + (size_t)t * a.B * a.n_classes);
-            pn[0] = bld(nr_, o_gn, 0);
-            if (ntc == 2) pn[1] = bld(nr_, o_gn + 64u, 0);
+        if constexpr (MODE == 0) {
+            if (cell) {
+                const rsrc_t nr_ = mk_rsrc(a.gumbel + (size_t)t * a.B * a.n_classes);
+                pn[0] = bld(nr_, o_gn, 0);
+                if (ntc == 2) pn[1] = bld(nr_, o_gn + 64u, 0);
+            }
+        } else if constexpr (MODE == 1) {
+            mol_draw(t + 1);
         }
         if (gcell) {
             const int tn = t + 1 < a.S ? t + 1 : t;
@@ -296,6 +350,8 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
             put(WP_HH, 2, 1, a1);
         }
         // ---- hop 2: y1 of every slot -> fc3 -> the slot's candidate of every row ------------
+        // (MOL / BETA: one tile; slots 2-31, for BETA 1-31, run it on their zero image, so every
+        // slot polls y1 at every step as in BITS and the sentinel protocol of y1 is unchanged)
         fail |= !g_poll<1>(xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid, cc, a.ctl, wh(3), (unsigned)t);
         {
             v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
@@ -311,9 +367,9 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
         if (fail) lds[WL_FAIL] = 1.f;
         gbar();
         if (v < 4) {
-            const unsigned want = key_tag(seq);
+            [[maybe_unused]] const unsigned want = key_tag(seq);
             float g1r = 0.f, g1z = 0.f, g1n = 0.f;
-            {
+            if constexpr (MODE == 0) {
                 // candidate: the max key (cand_key.h cand_key, l_k + G_k formed exactly) over the
                 // slot's classes of row cn: lane cul takes classes cpw w + 16 j + cul, j < ntc
                 uint32_t kh = 0, kl = 0;
@@ -332,6 +388,17 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
                 unsigned vo = cell && cul == 0 ? g_cand(cn, w) : kNoOff;
                 asm volatile("" : "+v"(vo));
                 __builtin_amdgcn_raw_buffer_store_b64((u2v){kh, kl | want}, xr, vo, GX_D * 4, 0);
+            } else {
+                // MOL / BETA: logit 16 w + cul of row cn (slots 0 and 1) as a tagged pair (float
+                // bits, seq), polled directly in hop 3; every lane issues the store (kNoOff: dropped)
+                float lg = 0.f;
+                if (o_lp != kNoOff) {
+                    lg = p_add(psum(WP_F3, 2, 0, cul), cb[32 + cul]);
+                    p_dbg_logit<DBG>(a.dbg, t, crow, 16 * w + cul, a.B, a.n_classes, lg);
+                }
+                unsigned vo = o_lp;
+                asm volatile("" : "+v"(vo));
+                __builtin_amdgcn_raw_buffer_store_b64((u2v){__float_as_uint(lg), seq}, xr, vo, GX_D * 4, 0);
             }
             if (gcell) {  // gh1 = W_hh1 h1 + b_hh1 of the cell's unit
                 g1r = p_add(psum(WP_HH, 2, 0, cul), cb[cul]);
@@ -340,7 +407,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
             }
             // ---- hop 3: sample of step t (lane cul polls slots 2 cul, 2 cul + 1 of row cn) ----
             float x;
-            {
+            if constexpr (MODE == 0) {
                 u4v q = {0u, want, 0u, want};
                 const unsigned t0s = p_now();
                 unsigned nsp = 0;
@@ -377,6 +444,83 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
                     __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u,
                                                           (unsigned)t * 2u, 0);
                     bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
+                }
+            } else {
+                // lane (row cn, cul) polls logits cul and 16 + cul of its row (tag: the whole seq);
+                // a lane without a logit loads from kNoOff (reads 0, not waited for)
+                unsigned va = l_ra ? g_logit(cn, cul) : kNoOff;
+                unsigned vb = l_rb ? g_logit(cn, 16 + cul) : kNoOff;
+                asm volatile("" : "+v"(va), "+v"(vb));
+                u2v qa, qb;
+                const unsigned t0s = p_now();
+                unsigned nsp = 0;
+                while (true) {
+                    qa = __builtin_amdgcn_raw_buffer_load_b64(xr, va, GX_D * 4, kCpNT);
+                    qb = __builtin_amdgcn_raw_buffer_load_b64(xr, vb, GX_D * 4, kCpNT);
+                    if (__all((!l_ra | (qa.y == seq)) & (!l_rb | (qb.y == seq)))) break;
+                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
+                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
+                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(5) | ((unsigned)v << 19)) == 0u) {
+                            a.ctl[PC_WHERE + 1] = 1u;
+                            a.ctl[PC_WHERE + 2] = (unsigned)t;
+                        }
+                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
+                        fail = true;
+                        break;
+                    }
+                }
+                const float la = __uint_as_float(qa.x);
+                [[maybe_unused]] const float lb = __uint_as_float(qb.x);
+                const int base = l & 48;  // lane 0 of this lane's row
+                if constexpr (MODE == 2) {
+                    // BETA (geneing 'RAW'): vocoder/distribution.py:7-20, Beta(exp l0, exp l1) on
+                    // [-1, 1] with the Philox gamma draws: lane 0 of the row draws X ~ Gamma(exp l0),
+                    // lane 1 Y ~ Gamma(exp l1) concurrently (philox.h gamma_mt, g = lane); lane 0
+                    // forms 2 X / (X + Y) - 1 exactly as beta_sample and k_persist_gen do
+                    double gv = 0.0;
+                    if (cell && cul < 2) {
+                        const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[cn];
+                        gv = gamma_mt((double)expf(la), (uint32_t)cul, (uint32_t)t, (uint32_t)ri.fold, ri.stream,
+                                      a.k0, a.k1);
+                    }
+                    const double gy = __shfl(gv, base + 1);
+                    float xv = 0.f;
+                    {
+#pragma clang fp contract(off)
+                        const float sb = (float)(gv / (gv + gy));
+                        xv = 2.0f * sb - 1.0f;
+                    }
+                    x = __shfl(xv, base);
+                } else {
+                    // MOL: k_persist_gen's operations in its order (kernels_persist_gen.hip, "MOL:";
+                    // vocoder/distribution.py:104-140)
+                    float bv;
+                    {
+#pragma clang fp contract(off)
+                        bv = cul < 10 ? la - pg : -INFINITY;
+                    }
+                    int bi = cul < 10 ? cul : 0x7fffffff;
+                    row16_argmax(bv, bi);  // first max over k < 10; every lane of the row gets it
+                    bi = bi < 10 ? bi : 0;
+                    // l[10 + bi]: the first value of lane 10 + bi, or the second of lane bi - 6
+                    const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
+                    const float mean = bi < 6 ? m0 : m1;
+                    float ls = __shfl(lb, base + 4 + bi);  // l[20 + bi]: the second value of lane 4 + bi
+                    const float lu = __shfl(pg, base + 10);
+                    {
+#pragma clang fp contract(off)
+                        const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
+                        ls = ls < lsmin ? lsmin : ls;
+                        x = mean + expf(ls) * lu;
+                        x = x < -1.f ? -1.f : x;
+                        x = x > 1.f ? 1.f : x;
+                    }
+                    pg = pgn;
+                }
+                if (w == 0 && cell && cul == 0) {
+                    int nn = cn;
+                    asm volatile("" : "+v"(nn));
+                    bst(x, mk_rsrc(a.samples), (unsigned)((g0 + kPG * nn) * a.ld) * 4u, (unsigned)t * 4u);
                 }
             }
             if (fail) lds[WL_FAIL] = 1.f;  // seen by every wave at the next step's check
@@ -419,21 +563,42 @@ hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s) {
     k_wide_gen_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf));
     return hipGetLastError();
 }
-int persist_wide_gen_scratch() {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, (const void*)k_persist_wide_gen<false>) != hipSuccess) return -1;
-    return (int)fa.localSizeBytes;
+// scratch bytes of the mode's instances (0 BITS, 1 MOL, 2 BETA): the larger of production and DBG
+int persist_wide_gen_scratch(int mode) {
+    hipFuncAttributes fa, fd;
+    const void* f = mode == 2 ? (const void*)k_persist_wide_gen<2, false>
+                  : mode == 1 ? (const void*)k_persist_wide_gen<1, false>
+                  : mode == 0 ? (const void*)k_persist_wide_gen<0, false> : nullptr;
+    const void* d = mode == 2 ? (const void*)k_persist_wide_gen<2, true>
+                  : mode == 1 ? (const void*)k_persist_wide_gen<1, true>
+                  : mode == 0 ? (const void*)k_persist_wide_gen<0, true> : nullptr;
+    if (!f || hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
+    if (mode == 0) return (int)fa.localSizeBytes;
+    if (hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
+    return (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
 }
 hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s) {
-    // whole launches of BITS rows (t0 = 0: x1, h1 of k_persist_gen_init), 512 or 1024 classes
-    // (1 or 2 fc3 tiles of 16 per slot); no rotated or time-sliced instance
-    if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || a.mode != 0 || a.t0 != 0 ||
-        a.t1 != a.S || a.vmap != nullptr || (a.n_classes != 512 && a.n_classes != 1024) ||
-        a.cpw * kPM != a.n_classes || a.wwide == nullptr)
+    // whole launches (t0 = 0: x1, h1 of k_persist_gen_init) of BITS rows with 512 or 1024 classes
+    // (1 or 2 fc3 tiles of 16 per slot), of MOL rows (30 logits) or of BETA rows (2): one tile in
+    // slots 0 and 1; no rotated or time-sliced instance
+    if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || a.t0 != 0 || a.t1 != a.S ||
+        a.vmap != nullptr || a.wwide == nullptr)
         return hipErrorInvalidValue;
     const size_t lb = persist_wide_gen_lds_bytes();
-    return a.dbg.out ? persist_launch<k_persist_wide_gen<true>>(lb, a, s)
-                     : persist_launch<k_persist_wide_gen<false>>(lb, a, s);
+    if (a.mode == 1) {  // (the draws come from the k_mol_noise stream)
+        if (a.cpw != 16 || a.n_classes != 30 || a.gumbel == nullptr) return hipErrorInvalidValue;
+        return a.dbg.out ? persist_launch<k_persist_wide_gen<1, true>>(lb, a, s)
+                         : persist_launch<k_persist_wide_gen<1, false>>(lb, a, s);
+    }
+    if (a.mode == 2) {
+        if (a.cpw != 16 || a.n_classes != 2) return hipErrorInvalidValue;
+        return a.dbg.out ? persist_launch<k_persist_wide_gen<2, true>>(lb, a, s)
+                         : persist_launch<k_persist_wide_gen<2, false>>(lb, a, s);
+    }
+    if (a.mode != 0 || (a.n_classes != 512 && a.n_classes != 1024) || a.cpw * kPM != a.n_classes)
+        return hipErrorInvalidValue;
+    return a.dbg.out ? persist_launch<k_persist_wide_gen<0, true>>(lb, a, s)
+                     : persist_launch<k_persist_wide_gen<0, false>>(lb, a, s);
 }
 
 // Exhaustive host check of the exchange layout (as wide_rr_layout_check): for every row count,
@@ -488,6 +653,58 @@ int wide_gen_layout_check(int R) {
             if (g_cand(n, 2 * c) % 16 || g_cand(n, 2 * c) + 16 > (unsigned)(kRowsW * kPM * 2) * 4u ||
                 g_cand(n, 2 * c + 1) != g_cand(n, 2 * c) + 8)
                 ++bad;
+    return bad;
+}
+
+// Host check of the MOL / BETA logit pairs (g_logit, n_logits 30 or 2) for a group of R rows:
+// every (row, logit) pair is 8-byte aligned inside the area at GX_D, written by exactly one lane
+// of the fc3 epilogue of exactly one slot (slot w < 2, lane cul: logit 16 w + cul < n_logits) and
+// read, in every slot, by exactly one hop-3 lane of the row (lane cul: logits cul and 16 + cul)
+// that expects that (row, logit); no two pairs overlap; the area lies after the vector slots,
+// inside the group's exchange area, in the part the reset zeroes; the no-logit offset fails the
+// range check. Returns the violations (-1: bad arguments).
+int wide_gen_mol_layout_check(int R, int n_logits) {
+    if (R < 1 || R > kRowsW || (n_logits != 30 && n_logits != 2)) return -1;
+    int bad = 0;
+    const int area = kRowsW * kPM * 2;  // floats
+    const int np = area / 2;
+    std::vector<int> wr(np, 0), id(np, -1);
+    for (int w = 0; w < kPM; ++w)
+        for (int cn = 0; cn < R; ++cn)
+            for (int cul = 0; cul < 16; ++cul) {
+                const int k = 16 * w + cul;
+                if (w >= 2 || k >= n_logits) continue;  // (the epilogue's o_lp)
+                const unsigned o = g_logit(cn, k);
+                if (o % 8 || o + 8 > (unsigned)area * 4u) { ++bad; continue; }
+                ++wr[o / 8];
+                id[o / 8] = cn * kGenLogitsMax + k;
+            }
+    for (int w = 0; w < kPM; ++w) {  // the readers of slot w
+        std::vector<int> rd(np, 0);
+        for (int cn = 0; cn < R; ++cn)
+            for (int cul = 0; cul < 16; ++cul)
+                for (int k = cul; k < n_logits && k < 32; k += 16) {
+                    const unsigned o = g_logit(cn, k);
+                    if (o % 8 || o + 8 > (unsigned)area * 4u) { ++bad; continue; }
+                    ++rd[o / 8];
+                    if (id[o / 8] != cn * kGenLogitsMax + k) ++bad;  // the reader expects another (row, logit)
+                }
+        for (int i = 0; i < np; ++i)
+            if (rd[i] > 1 || rd[i] != wr[i]) ++bad;
+    }
+    int pairs = 0;
+    for (int i = 0; i < np; ++i) {
+        if (wr[i] > 1) ++bad;
+        pairs += wr[i];
+    }
+    if (pairs != R * n_logits) ++bad;
+    // disjoint from the vector slots, inside the group's area, where the reset writes zeros
+    const int bufs[3] = {GX_X1, GX_H1, GX_Y1}, szs[3] = {GS_X, GS_X, GS_Y};
+    for (int b = 0; b < 3; ++b)
+        for (unsigned sq = 0; sq < 2; ++sq)
+            if (g_slot(bufs[b], szs[b], sq) + (unsigned)szs[b] * 4u > (unsigned)GX_D * 4u) ++bad;
+    if (GX_D + area > GX_GROUP || GX_D % 2) ++bad;
+    if ((unsigned long long)kNoOff + (unsigned long long)GX_D * 4ull + 8ull <= 0x7fffffffull) ++bad;
     return bad;
 }
 

@@ -143,6 +143,12 @@ struct PlanRates {
     // 3.594 / 3.634 us at 5 / 9 / 16 rows per group (profiles/wide_gen/gen_wide_r*.log, least
     // squares: tools/make_rates.py)
     double wide_gen[2] = {3.508, 0.0082};
+    // the geneing continuous heads on the same kernel, base + row x r: MOL (30 logits) 3.067 /
+    // 3.116 / 3.172 us, Beta (2 logits, float64 gamma draws) 4.993 / 5.156 / 5.361 us at 5 / 9 / 16
+    // rows per group (profiles/wide_gen_mol/gen_{mol,beta}_wide_r*.log, least squares:
+    // tools/make_rates.py)
+    double wide_gen_mol[2] = {3.025, 0.0094};
+    double wide_gen_beta[2] = {4.84, 0.033};
     double slice[2] = {60.0, 0.98};                        // us per extra launch, gain threshold
     // rotation: rates of the rotated instance's two bodies by rows per group (the (q + 1)-row
     // one at its single-launch rate; the q-row one the best split measured, §3.0e)
@@ -252,7 +258,7 @@ struct wrnn_handle {
         const float *wwide = nullptr, *wwide_lds = nullptr;  // wide-row launches (MFMA images)
         const float* wfc3b = nullptr;  // ... > 512 classes: the second fc3 tile (L2-streamed)
         const float* wwide_rr = nullptr;  // runtimeracer wide-row launches (kernels_persist_wide_rr.hip)
-        const float* wwide_gen = nullptr;  // geneing BITS wide-row launches (kernels_persist_wide_gen.hip)
+        const float* wwide_gen = nullptr;  // geneing BITS / MOL / Beta wide-row launches (kernels_persist_wide_gen.hip)
         // sparse k_persist image (pruned checkpoints, pack_persist_sparse):
         // per-lane masks / list bases [kPM][kPT] uint4 and the block lists [kPM][kPLdsW4] float4
         bool sp_ok = false;
@@ -1082,13 +1088,17 @@ int pack_persist_gen(wrnn_handle* h, int oF1) {
 // of unit 8 w + m (m < 8) | gate z of unit 8 w + m - 8, T1 = gate n of unit 8 w + m (m < 8) | 0,
 // T2 = fc1[:, :256] row 4 w + m (m < 4) | 0. fc3 tiles j = 0, 1 (K = 128), k-step ks < 4: fc3 row
 // cpw w + 16 j + m, input 16 v + 4 c + ks at [w][v][6 + j][l] component ks; cpw = n / 32.
+// MOL (n = 30) / BETA (n = 2): cpw = 16, one fc3 tile, rows >= n zero (slots 2-31 hold a zero image).
 int pack_persist_wide_gen(wrnn_handle* h) {
     auto& T = h->host;
     auto& P = h->pw;
     P.wwide_gen = nullptr;
     const int H = h->H, F = h->F, A = h->A, n = h->n_classes;
-    if (h->cfg.mode != WRNN_MODE_RAW || H != kRH || F != kGF || (n != 512 && n != 1024)) return WRNN_OK;
-    const int cpw = n / kPM;
+    const int mode = h->cfg.mode;
+    const bool bits = mode == WRNN_MODE_RAW && (n == 512 || n == 1024);
+    const bool cont = (mode == WRNN_MODE_MOL && n == 30) || (mode == WRNN_MODE_BETA && n == 2);
+    if (H != kRH || F != kGF || !(bits || cont)) return WRNN_OK;
+    const int cpw = bits ? n / kPM : 16;
     const auto& Whh = T["rnn1.weight_hh_l0"];
     const auto& Wf1 = T["fc1.weight"];
     const auto& Wf3 = T["fc3.weight"];
@@ -1108,7 +1118,8 @@ int pack_persist_wide_gen(wrnn_handle* h) {
                 }
                 for (int j = 0; j < cpw / 16; ++j)
                     for (int ks = 0; ks < 4; ++ks)
-                        d[(6 + j) * 256 + ks] = Wf3[(size_t)(cpw * w + 16 * j + m) * F + 16 * v + 4 * c + ks];
+                        if (cpw * w + 16 * j + m < n)
+                            d[(6 + j) * 256 + ks] = Wf3[(size_t)(cpw * w + 16 * j + m) * F + 16 * v + 4 * c + ks];
             }
     int rc = WRNN_OK;
     P.wwide_gen = upload(h, wr, &rc);
@@ -2534,7 +2545,9 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             ag.prog_base = a.prog_base;
             if (L.wide) {
                 PersistGenArgs aw = ag;
-                aw.cpw = n / kPM;  // classes per slot of the wide layout (every class owned: n = 32 cpw)
+                // classes per slot of the wide layout (BITS: every class owned, n = 32 cpw; MOL /
+                // Beta: one tile of 16 in slots 0 and 1)
+                aw.cpw = a.mode == WRNN_MODE_RAW ? n / kPM : 16;
                 le = launch_persist_wide_gen(aw, st);
             } else {
                 le = launch_persist_gen(ag, st);
@@ -2766,6 +2779,8 @@ static const RateKey kRateKeys[] = {
     {"wide_rr", nullptr, nullptr, nullptr, &PlanRates::wide_rr},
     {"wide_rr_mol", nullptr, nullptr, nullptr, &PlanRates::wide_rr_mol},
     {"wide_gen", nullptr, nullptr, nullptr, &PlanRates::wide_gen},
+    {"wide_gen_mol", nullptr, nullptr, nullptr, &PlanRates::wide_gen_mol},
+    {"wide_gen_beta", nullptr, nullptr, nullptr, &PlanRates::wide_gen_beta},
     {"slice", nullptr, nullptr, nullptr, &PlanRates::slice},
     {"rot9", nullptr, &PlanRates::rot9, nullptr, nullptr},
     {"rot9_sp", nullptr, &PlanRates::rot9_sp, nullptr, nullptr},
@@ -2874,6 +2889,8 @@ struct PlanIn {
     bool has_wide = false, has_wide_rr = false;  // (has_wide: RAW or MOL images; has_wide_rr: RAW only)
     bool has_wide_rr_mol = false;  // runtimeracer MOL image (30 logits)
     bool has_wide_gen = false;     // geneing BITS image (512 / 1024 classes)
+    bool has_wide_gen_mol = false;   // geneing MOL image (30 logits)
+    bool has_wide_gen_beta = false;  // geneing Beta image (2 logits)
     int scr[2][kPNR + 1] = {};     // fatchord k_persist [stream | ring][nr]
     int scr_sp[kPNR + 1] = {};     // sparse instances
     int scr_rot[2][kPNR + 1] = {}; // rotated instance of this topology / mode [dense | sparse][nr]
@@ -2974,6 +2991,17 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
                 (in.wmode == 1 || B > kPG * kPNR) && (in.wide_scr == 0 || in.allow_wide_scratch)) {
                 if (in.wmode == 1) opts.clear();
                 for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, R.wide_gen[0] + R.wide_gen[1] * r});
+            }
+            // geneing MOL / Beta: the same rule, each head by its own image and its own key (the
+            // MOL instances run spill-free; the Beta ones may keep the frame k_persist_gen BETA is
+            // accepted with, at most 16 bytes)
+            const bool gen_mol = in.gen && in.has_wide_gen_mol && in.mode == WRNN_MODE_MOL;
+            const bool gen_beta = in.gen && in.has_wide_gen_beta && in.mode == WRNN_MODE_BETA;
+            if ((gen_mol || gen_beta) && in.wmode && (in.wmode == 1 || B > kPG * kPNR) &&
+                ((in.wide_scr >= 0 && in.wide_scr <= (gen_beta ? 16 : 0)) || in.allow_wide_scratch)) {
+                const double* k = gen_mol ? R.wide_gen_mol : R.wide_gen_beta;
+                if (in.wmode == 1) opts.clear();
+                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, k[0] + k[1] * r});
             }
         }
         if (in.nr_max > 0) {  // diagnostic: variant A/B (WRNN_PERSIST_NR_MAX)
@@ -3104,6 +3132,8 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
     in.has_wide_rr = W.rr && W.wwide_rr != nullptr && in.mode == WRNN_MODE_RAW;
     in.has_wide_rr_mol = W.rr && W.wwide_rr != nullptr && in.mode == WRNN_MODE_MOL;
     in.has_wide_gen = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_RAW;
+    in.has_wide_gen_mol = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_MOL;
+    in.has_wide_gen_beta = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_BETA;
     if (!W.ok) return in;
     for (int c = 1; c <= kPNR; ++c) {
         if (in.fat) {
@@ -3125,8 +3155,8 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
     } else if (in.has_wide_rr || in.has_wide_rr_mol) {
         in.wide_scr = persist_wide_rr_scratch(in.has_wide_rr_mol);
         in.wide_rot_scr = persist_wide_rr_rot_scratch(in.has_wide_rr_mol);
-    } else if (in.has_wide_gen) {
-        in.wide_scr = persist_wide_gen_scratch();
+    } else if (in.has_wide_gen || in.has_wide_gen_mol || in.has_wide_gen_beta) {
+        in.wide_scr = persist_wide_gen_scratch(in.mode);
     }
     if (const char* e = std::getenv("WRNN_PERSIST_WIDE")) in.wmode = std::atoi(e);
     if (const char* e = std::getenv("WRNN_PERSIST_NR_MAX")) in.nr_max = std::atoi(e);
@@ -3774,6 +3804,12 @@ int wrnn_debug_wide_gen_layout(int rows_per_group) {
     return bad;
 }
 
+int wrnn_debug_wide_gen_mol_layout(int rows_per_group, int n_logits) {
+    const int bad = wide_gen_mol_layout_check(rows_per_group, n_logits);
+    if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..16 and n_logits 30 (MOL) or 2 (Beta)");
+    return bad;
+}
+
 int wrnn_debug_wide_mol_layout(int rows_per_group) {
     const int bad = wide_mol_layout_check(rows_per_group);
     if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..16");
@@ -3870,7 +3906,8 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     in.S = seq_len;
     // flags: 1 sparse image, 2 P1 ring / per-frame P1 (fatchord, runtimeracer), 4 wide images
     // (fatchord RAW / MOL, runtimeracer RAW, geneing BITS with 512 or 1024 classes), 16 the
-    // runtimeracer MOL wide image; every variant spill-free
+    // runtimeracer MOL wide image, 32 the geneing MOL wide image, 64 the geneing Beta wide image;
+    // every variant spill-free
     in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.force_sp = in.sp && (flags & 8);
     in.p1ring = in.fat && (flags & 2);
@@ -3879,6 +3916,8 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     in.has_wide_rr = in.rr && (flags & 4) && mode == WRNN_MODE_RAW;
     in.has_wide_rr_mol = in.rr && (flags & 16) && mode == WRNN_MODE_MOL;
     in.has_wide_gen = in.gen && (flags & 4) && mode == WRNN_MODE_RAW && (in.n == 512 || in.n == 1024);
+    in.has_wide_gen_mol = in.gen && (flags & 32) && mode == WRNN_MODE_MOL;
+    in.has_wide_gen_beta = in.gen && (flags & 64) && mode == WRNN_MODE_BETA;
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
     PlanOut out;
     plan_call(in, R, out);

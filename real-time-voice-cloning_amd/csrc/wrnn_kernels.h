@@ -403,14 +403,18 @@ struct PersistGenArgs {
 hipError_t launch_persist_gen(const PersistGenArgs& a, hipStream_t s);
 // Wide-row geneing launch (kernels_persist_wide_gen.hip): up to kPWideRows rows per XCD group,
 // the 32 slots alike (8 GRU units, 4 fc1 outputs, n / 32 classes each), fp32 MFMA products,
-// BITS (RAW categorical) with 512 or 1024 classes.
+// BITS (RAW categorical) with 512 or 1024 classes, or the continuous heads (MOL: 30 logits, BETA:
+// 2; cpw = 16: one fc3 tile in slots 0 and 1, the logits exchanged as tagged pairs in the
+// candidate area). Dispatches on a.mode.
 hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s);
 size_t persist_wide_gen_lds_bytes();
 size_t persist_wide_gen_xbuf_floats();
 size_t persist_wide_gen_wreg_floats();
 hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s);
-int persist_wide_gen_scratch();
+int persist_wide_gen_scratch(int mode);  // scratch bytes of the mode's instances (0 BITS, 1 MOL, 2 BETA)
 int wide_gen_layout_check(int rows_per_group);
+// host: violations of the MOL (30) / BETA (2) logit-pair layout; -1 for bad arguments
+int wide_gen_mol_layout_check(int rows_per_group, int n_logits);
 int persist_gen_rot_scratch(int nr, int mode);  // the rotated BITS / MOL instance's scratch bytes (-1: none)
 hipError_t launch_persist_gen_init(const PersistGenArgs& a, hipStream_t s);
 int persist_gen_variant_ok(int nr, int cpw, int mode);

@@ -41,7 +41,7 @@ EXPORTED = [
     'wrnn_debug_beta', 'wrnn_debug_decide', 'wrnn_debug_rot_plan', 'wrnn_debug_slice_plan', 'wrnn_rot_info', 'wrnn_persist_steps', 'wrnn_plan_info', 'wrnn_debug_p1', 'wrnn_get_stream',
     'wrnn_set_utt_streams', 'wrnn_set_fold_ranges', 'wrnn_set_debug_steps', 'wrnn_debug_logits', 'wrnn_debug_wide_layout',
     'wrnn_debug_wide_mol_layout', 'wrnn_debug_wide_gen_layout', 'wrnn_debug_wide_rr_mol_layout',
-    'wrnn_sparse_info', 'wrnn_set_rates', 'wrnn_get_rates', 'wrnn_debug_plan',
+    'wrnn_debug_wide_gen_mol_layout', 'wrnn_sparse_info', 'wrnn_set_rates', 'wrnn_get_rates', 'wrnn_debug_plan',
 ]
 
 
@@ -157,6 +157,7 @@ def load_library(path=None):
         'wrnn_debug_wide_mol_layout': (c_int, [c_int]),
         'wrnn_debug_wide_gen_layout': (c_int, [c_int]),
         'wrnn_debug_wide_rr_mol_layout': (c_int, [c_int]),
+        'wrnn_debug_wide_gen_mol_layout': (c_int, [c_int, c_int]),
         'wrnn_debug_logits': (c_int, [c_void_p, c_int, c_int, P(ctypes.c_float), c_size_t]),
     }
     # (an A/B build given by WRNN_LIB may predate an entry point: it is left unbound)

@@ -18,6 +18,9 @@ time) and writes `key v1 .. v4` lines for the keys it found; the runtime
     at least two fills) -> wide_gen = base, per row (least squares)
   <dir>/rr_mol_wide_r<k>.log (runtimeracer MOL, every launch wide at k rows per group,
     WRNN_PERSIST_WIDE=1; at least two fills) -> wide_rr_mol = base, per row (least squares)
+  <dir>/gen_mol_wide_r<k>.log, <dir>/gen_beta_wide_r<k>.log (geneing MOL / Beta ('RAW'), every launch
+    wide at k rows per group, WRNN_PERSIST_WIDE=1; at least two fills) -> wide_gen_mol,
+    wide_gen_beta = base, per row (least squares)
 Later directories override earlier ones. The rotation tables keep the runtime's defaults unless
 a key is already in the file given as OUT (kept lines are carried over).
 """
@@ -83,6 +86,15 @@ def main():
             per_row = max(per_row, 0.001)
             keys['wide_rr_mol'] = [round(mv - per_row * mk, 3), round(per_row, 4)]
             src['wide_rr_mol'] = d
+        for pre, key in (('gen_mol_wide_r', 'wide_gen_mol'), ('gen_beta_wide_r', 'wide_gen_beta')):
+            pts = [(k, us_step(line_of(os.path.join(d, f'{pre}{k}.log')))) for k in range(1, 17)]
+            pts = [(k, v) for k, v in pts if v is not None]
+            if len(pts) >= 2:
+                mk, mv = sum(k for k, _ in pts) / len(pts), sum(v for _, v in pts) / len(pts)
+                per_row = sum((k - mk) * (v - mv) for k, v in pts) / sum((k - mk) ** 2 for k, _ in pts)
+                per_row = max(per_row, 0.001)
+                keys[key] = [round(mv - per_row * mk, 3), round(per_row, 4)]
+                src[key] = d
     kept = []
     if os.path.exists(out):
         for ln in open(out):
