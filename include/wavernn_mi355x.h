@@ -237,6 +237,24 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
  * at most `cap` entries are written. 0 launches after a CHAIN call. */
 int wrnn_plan_info(wrnn_handle* h, int* n_launches, int* first_row, int* rows_per_group, int* wide,
                    int cap);
+/* Per-step conditioning / noise streams of the last call (operator introspection): the bytes of
+ * the P1 stream [seq_len][rows][4 rnn_dims] and of the noise stream (RAW: Gumbel words
+ * [seq_len][rows][n_classes], MOL: [seq_len][rows][12]; the stream's extent, rows padded to the
+ * plan) the call wrote to device memory before its launches. *p1_bytes is 0 when only step 0 was
+ * formed (every launch forms P1 in-kernel), *noise_bytes is 0 when every launch draws in-kernel
+ * (and for the Beta head). Both 0 after a call that ran on CHAIN, a fallen-back one included. A geneing call whose launches are all wide
+ * forms both in-kernel (env WRNN_GEN_RING=0, read per call, keeps the streams; =1 forces the
+ * in-kernel form wherever it is possible); a geneing call with a register-resident launch keeps
+ * its streams. */
+int wrnn_stream_info(wrnn_handle* h, uint64_t* p1_bytes, uint64_t* noise_bytes);
+/* Host-only (no device): the same two figures for the call wrnn_debug_plan describes under the
+ * built-in rates (arguments and flags as there), and whether the workspace check would admit the
+ * persistent engine (*persist_ok; 0: an engine='auto' call runs on CHAIN). One more flag: 128 =
+ * geneing in-kernel conditioning available (the per-frame P1 form and spill-free ring instances,
+ * as on a finalized geneing handle); without it a geneing call is taken to write its streams. No
+ * environment switch is read: the default rule. wrnn_generate runs the same function. */
+int wrnn_debug_stream_bytes(int model_type, int bits, int mode, int rows, int seq_len, int flags,
+                            double* p1_bytes, double* noise_bytes, int* persist_ok);
 
 /* Per-stage timing of the dominant recurrent kernel. Enable before a call; read after:
  * average duration in microseconds of the launches of stage `stage` in the last call, and

@@ -34,9 +34,13 @@
 // Vectors travel as 16-byte packets in MFMA B-operand order, untagged, with a sentinel-reset
 // slot pair per vector (the protocol of kernels_persist_wide_rr.hip; DESIGN.md §3.0d, the
 // buffer-ordering table of this kernel is in §3.0c). Candidates are the two-word keys of
-// cand_key.h, tagged with the step. The Gumbel noise [S][B][n] and P1 [S][B][256][4] are read
-// from the call's streams as k_persist_gen reads them: a 64-bit base per step (uniform) plus a
-// 32-bit offset inside the step.
+// cand_key.h, tagged with the step. Stream instances (RING false) read the Gumbel noise [S][B][n]
+// and P1 [S][B][256][4] from the call's streams as k_persist_gen reads them: a 64-bit base per step
+// (uniform) plus a 32-bit offset inside the step. Ring instances (RING true; calls whose launches
+// are all wide) form both in-kernel: waves 4-7, which own no epilogue cell, write the slot's P1
+// (ring_p1_make, from the per-frame tables) and its Gumbel words (ring_noise_make, BITS only) into one-slot
+// LDS arrays that waves 0-3 read -- every value is produced and consumed by the same workgroup, so
+// the two workgroup barriers of the step order them and nothing new crosses workgroups.
 //
 // MOL / Beta (MODE 1 / 2): fc3 has 30 / 2 outputs, so it is one 16-row tile per slot (cpw = 16):
 // slots 0 and 1 hold logit rows 16 w + m (Beta: slot 0 rows 0 and 1), every other slot runs the
@@ -60,6 +64,7 @@
 #include "persist_common.h"
 #include "philox.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace wrnn {
@@ -115,6 +120,11 @@ constexpr int WL_CB = 128;       // b_hh1 of the slot's units [3][8], then b_f3 
 constexpr int WL_P = 256;        // partial tiles [8 v][nt][16 n][16 m], one buffer per product
 constexpr int WT = 8 * 256;
 constexpr int WP_F1 = WL_P, WP_HH = WP_F1 + WT, WP_F3 = WP_HH + 2 * WT, WL_TOTAL = WP_F3 + 2 * WT;
+// ring instances: P1 of the next step as float4 [16 n][8 units], the step's Gumbel words
+// [16 n][32 (cpw 16: the first 16)] -- one slot each, behind the partial tiles
+constexpr int kGrW = 32;
+constexpr int WL_P1R = WL_TOTAL, WL_GR = WL_P1R + kRowsW * GU * 4, WL_TOTAL_RING = WL_GR + kRowsW * kGrW;
+static_assert(WL_P1R % 4 == 0 && WL_TOTAL_RING * sizeof(float) <= 64 * 1024, "ring arrays: float4-aligned, inside LDS");
 static_assert(sizeof(RowInfo) == 24 && kRowsW * 6 <= WL_FAIL, "RowInfo array overflows");
 static_assert(WL_CB + 32 + 32 <= WL_P, "slot constants overflow");
 
@@ -165,13 +175,78 @@ __device__ __forceinline__ bool g_poll(rsrc_t xr, unsigned voff, unsigned so, bo
     }
 }
 
+// ---- ring instances: the slot's per-step operands, formed by waves 4-7 into the one-slot LDS
+// arrays; produced and consumed by the same workgroup only ------------------------------------
+// The Gumbel word of (tau, row n, class) as k_gumbel forms it (philox.h gumbel_q_of, keyed by
+// class quad, absolute step, fold, stream). Thread j of a row takes class j of slot w (cpw 16,
+// ntc 1) or the pair 2 j, 2 j + 1 (cpw 32, ntc 2: one Philox block for both).
+__device__ __forceinline__ void ring_noise_make(const PersistGenRingArgs& a, float* lds, int w, int ntc, int n,
+                                                int j, int tau) {
+    int c = a.cpw * w + (ntc == 2 ? 2 * j : j);
+    asm volatile("" : "+v"(c));
+    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[n];
+    // (a padding row repeats the last real row: drawn and never used)
+    const U4 o = philox4x32_10((uint32_t)(c >> 2), (uint32_t)tau, (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
+    const int q = c & 3;
+    const uint32_t wd = q == 0 ? o.x : q == 1 ? o.y : q == 2 ? o.z : o.w;
+    float* dst = lds + WL_GR + n * kGrW + (ntc == 2 ? 2 * j : j);
+    dst[0] = __uint_as_float(gumbel_q_of(wd));
+    if (ntc == 2) {  // class c + 1 of the same quad (c is even)
+        __builtin_amdgcn_sched_barrier(0);
+        dst[1] = __uint_as_float(gumbel_q_of(q == 0 ? o.y : o.w));
+    }
+}
+// P1(tau) of (row n, unit 8 w + j) from the per-frame tables, k_p1_expand's fma chain without its
+// zero tap (as kernels_persist_wide.hip p1_make): positions >= L take the zero frame at fbase
+// (bias only), frames outside the utterance its zeroed guard slots; tau is clamped at the row's
+// last step, as the stream read clamps it.
+__device__ __forceinline__ void ring_p1_make(const PersistGenRingArgs& a, float* lds, int w, int n, int j, int tau) {
+    const int tc = tau < a.S ? tau : a.S - 1;
+    int uu = GU * w + j;
+    asm volatile("" : "+v"(uu));
+    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[n];
+    const unsigned p = (unsigned)(ri.rel0 + tc);
+    const bool in = p < (unsigned)ri.L;  // else the zero tail pad: bias only (zero frame)
+    const unsigned f = p / (unsigned)a.hop, sph = in ? p - f * (unsigned)a.hop : 0u;
+    const unsigned s0 = in ? (unsigned)ri.fbase - 1u + f + (sph >= (unsigned)a.p1split ? 1u : 0u)
+                           : (unsigned)ri.fbase;
+    constexpr unsigned kRow = 4u * GH * 4u;  // bytes per frame slot
+    const unsigned col = (unsigned)uu * 16u;
+    const float4 tk = __builtin_bit_cast(
+        float4, __builtin_amdgcn_raw_buffer_load_b128(mk_rsrc(a.p1taps), sph * 16u, 0, 0));
+    const rsrc_t qr = mk_rsrc(a.p1q);
+    float4 tq[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        tq[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                               qr, (in ? s0 + (unsigned)k : s0) * kRow + col, 0, 0));
+    const float4 ta = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                     mk_rsrc(a.p1a), (in ? (unsigned)ri.fbase + 1u + f : s0) * kRow + col, 0, 0));
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float kk[4] = {tk.x, tk.y, tk.z, tk.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        m.x = fmaf(kk[k], tq[k].x, m.x);
+        m.y = fmaf(kk[k], tq[k].y, m.y);
+        m.z = fmaf(kk[k], tq[k].z, m.z);
+        m.w = fmaf(kk[k], tq[k].w, m.w);
+    }
+    reinterpret_cast<float4*>(lds + WL_P1R)[n * GU + j] =
+        make_float4(p_add(m.x, ta.x), p_add(m.y, ta.y), p_add(m.z, ta.z), p_add(m.w, ta.w));
+}
+
 }  // namespace
 
 // MODE: 0 BITS (categorical), 1 MOL, 2 BETA (geneing 'RAW'); each its own instantiation (the BETA
 //       float64 gamma sampler would otherwise raise the other instances' register allocation)
+// RING: P1 (every head) and the Gumbel noise (BITS) formed in-kernel into LDS instead of read from
+//       the call's streams (MOL keeps its k_mol_noise stream). A ring instance takes
+//       PersistGenRingArgs (the per-frame tables behind the common arguments); the stream
+//       instances keep PersistGenArgs, so their code is what it was before the ring existed
 // DBG: the instance that records logits for the teacher-forced gate (wrnn_set_debug_steps)
-template <int MODE, bool DBG>
-__global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
+template <int MODE, bool RING, bool DBG>
+__global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(
+    std::conditional_t<RING, PersistGenRingArgs, PersistGenArgs> a) {
     static_assert(MODE >= 0 && MODE <= 2, "BITS, MOL or BETA");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int* sreg = reinterpret_cast<int*>(lds + WL_REG);
@@ -278,7 +353,20 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
     [[maybe_unused]] const bool l_ra = cell && cul < a.n_classes, l_rb = cell && 16 + cul < a.n_classes;
     [[maybe_unused]] const unsigned o_lp =
         cell && w < 2 && 16 * w + cul < a.n_classes ? g_logit(cn, 16 * w + cul) : kNoOff;
+    // ring instances: thread i of waves 4-7 forms the P1 cell (row i / 8, unit i % 8) for i < 8 R
+    // and, BITS, the noise cell (row i / 16, thread i % 16 of the row) for i < 16 R (ring_p1_make,
+    // ring_noise_make above) into the one-slot LDS arrays
+    [[maybe_unused]] auto ring_make = [&](const PersistGenRingArgs& ra, int t_noise, int t_p1) {
+        const int i = tid - 256;
+        if (i < GU * R) ring_p1_make(ra, lds, w, i >> 3, i & 7, t_p1);
+        if constexpr (MODE == 0)
+            if (i < 16 * R) ring_noise_make(ra, lds, w, ntc, i >> 4, i & 15, t_noise);
+    };
     __syncthreads();
+    // ring prologue: the noise of step t0 and P1(t0 + 1) (step t forms the noise of t + 1 and
+    // P1(t + 2)); waves 0-3 read them after step t0's first barrier
+    if constexpr (RING)
+        if (v >= 4) ring_make(a, a.t0, a.t0 + 1);
     if constexpr (MODE == 1) {  // the draws of step t0 (the loop loads those of t + 1 at step t)
         mol_draw(a.t0);
         pg = pgn;
@@ -303,7 +391,8 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
             const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[cn];
             pc = bld(fcr, (unsigned)(p_frame(ri, t, a.hop) * a.cond_width + a.oF1 + GO * w + cul) * 4u, 0);
         }
-        if constexpr (MODE == 0) {
+        // (ring instances: pn and pp come from the LDS arrays after this step's first barrier)
+        if constexpr (MODE == 0 && !RING) {
             if (cell) {
                 const rsrc_t nr_ = mk_rsrc(a.gumbel + (size_t)t * a.B * a.n_classes);
                 pn[0] = bld(nr_, o_gn, 0);
@@ -312,10 +401,12 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
         } else if constexpr (MODE == 1) {
             mol_draw(t + 1);
         }
-        if (gcell) {
-            const int tn = t + 1 < a.S ? t + 1 : t;
-            pp = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                mk_rsrc(a.P1 + ((size_t)tn * a.B + g0) * 4 * GH), o_p1, 0, 0));
+        if constexpr (!RING) {
+            if (gcell) {
+                const int tn = t + 1 < a.S ? t + 1 : t;
+                pp = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                    mk_rsrc(a.P1 + ((size_t)tn * a.B + g0) * 4 * GH), o_p1, 0, 0));
+            }
         }
         // ---- hop 1: x1 of every slot -> fc1 -> y1 -------------------------------------------
         fail |= !g_poll<2>(xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid, cc, a.ctl, wh(1), (unsigned)t);
@@ -335,6 +426,18 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
                 y = y > 0.f ? y : 0.f;
             }
             pub(GX_Y1, GS_Y, o_py, y, seq);
+            if constexpr (RING) {
+                // the slot's noise of step t and P1(t + 1): written by waves 4-7 before the barrier
+                // above (step t - 1's tail, or the prologue), overwritten only after the barrier
+                // below
+                if constexpr (MODE == 0) {
+                    if (cell) {
+                        pn[0] = lds[WL_GR + cn * kGrW + cul];
+                        if (ntc == 2) pn[1] = lds[WL_GR + cn * kGrW + 16 + cul];
+                    }
+                }
+                if (gcell) pp = reinterpret_cast<const float4*>(lds + WL_P1R)[cn * GU + cul];
+            }
         }
         // ---- in the wait for y1: h1 of every slot -> W_hh1 h1 (GRU1 at this step's end) ------
         fail |= !g_poll<2>(xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid, cc, a.ctl, wh(2), (unsigned)t);
@@ -533,6 +636,11 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
             }
             pub(GX_X1, GS_X, o_px, x1, seq + 1u);
             pub(GX_H1, GS_X, o_px, h1r, seq + 1u);
+        } else if constexpr (RING) {
+            // waves 4-7: the noise of step t + 1 and P1(t + 2) into the one-slot LDS arrays, while
+            // waves 0-3 run the fc3 epilogue, hop 3 and GRU1 (they read the step-t values before
+            // the barrier above and read the new ones after the next step's first barrier)
+            ring_make(a, t + 1, t + 2);
         }
         if (w == 0 && tid == 0) {
             if (g == 0) p_progress(a.progress, a.prog_base, t);
@@ -546,7 +654,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(PersistGenArgs a) {
 // at least 96 KB so that no CU can take two workgroups of this (register-light) kernel: every
 // group must span 32 CUs
 size_t persist_wide_gen_lds_bytes() {
-    const size_t need = (size_t)WL_TOTAL * sizeof(float);
+    const size_t need = (size_t)WL_TOTAL_RING * sizeof(float);  // (the stream instances use WL_TOTAL of it)
     return need > 96 * 1024 ? need : 96 * 1024;
 }
 size_t persist_wide_gen_xbuf_floats() { return (size_t)kPG * GX_GROUP; }
@@ -563,21 +671,47 @@ hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s) {
     k_wide_gen_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf));
     return hipGetLastError();
 }
-// scratch bytes of the mode's instances (0 BITS, 1 MOL, 2 BETA): the larger of production and DBG
+namespace {
+template <bool RING, bool DBG>
+const void* wide_gen_fn(int mode) {
+    return mode == 2 ? (const void*)k_persist_wide_gen<2, RING, DBG>
+         : mode == 1 ? (const void*)k_persist_wide_gen<1, RING, DBG>
+         : mode == 0 ? (const void*)k_persist_wide_gen<0, RING, DBG> : nullptr;
+}
+const void* wide_gen_fn(int mode, bool ring, bool dbg) {
+    return ring ? (dbg ? wide_gen_fn<true, true>(mode) : wide_gen_fn<true, false>(mode))
+                : (dbg ? wide_gen_fn<false, true>(mode) : wide_gen_fn<false, false>(mode));
+}
+}  // namespace
+// scratch bytes of the mode's stream instances (0 BITS, 1 MOL, 2 BETA): the larger of production
+// and DBG (BITS: the production instance, as the planner has always read it)
 int persist_wide_gen_scratch(int mode) {
     hipFuncAttributes fa, fd;
-    const void* f = mode == 2 ? (const void*)k_persist_wide_gen<2, false>
-                  : mode == 1 ? (const void*)k_persist_wide_gen<1, false>
-                  : mode == 0 ? (const void*)k_persist_wide_gen<0, false> : nullptr;
-    const void* d = mode == 2 ? (const void*)k_persist_wide_gen<2, true>
-                  : mode == 1 ? (const void*)k_persist_wide_gen<1, true>
-                  : mode == 0 ? (const void*)k_persist_wide_gen<0, true> : nullptr;
+    const void* f = wide_gen_fn(mode, false, false);
+    const void* d = wide_gen_fn(mode, false, true);
     if (!f || hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
     if (mode == 0) return (int)fa.localSizeBytes;
     if (hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
     return (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
 }
-hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s) {
+// ... and of its ring instances (the larger of production and DBG): a ring launch needs 0. A
+// constant of the build, read from the code objects once per mode
+int persist_wide_gen_ring_scratch(int mode) {
+    if (mode < 0 || mode > 2) return -1;
+    static int cached[3] = {-2, -2, -2};  // -2: not read yet
+    if (cached[mode] == -2) {
+        hipFuncAttributes fa, fd;
+        const void* f = wide_gen_fn(mode, true, false);
+        const void* d = wide_gen_fn(mode, true, true);
+        if (hipFuncGetAttributes(&fa, f) != hipSuccess || hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
+        cached[mode] = (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
+    }
+    return cached[mode];
+}
+namespace {
+// the checks common to both forms, then the head's instance K<MODE, DBG>
+template <bool RING, typename Args>
+hipError_t wide_gen_launch(const Args& a, hipStream_t s) {
     // whole launches (t0 = 0: x1, h1 of k_persist_gen_init) of BITS rows with 512 or 1024 classes
     // (1 or 2 fc3 tiles of 16 per slot), of MOL rows (30 logits) or of BETA rows (2): one tile in
     // slots 0 and 1; no rotated or time-sliced instance
@@ -587,18 +721,30 @@ hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s) {
     const size_t lb = persist_wide_gen_lds_bytes();
     if (a.mode == 1) {  // (the draws come from the k_mol_noise stream)
         if (a.cpw != 16 || a.n_classes != 30 || a.gumbel == nullptr) return hipErrorInvalidValue;
-        return a.dbg.out ? persist_launch<k_persist_wide_gen<1, true>>(lb, a, s)
-                         : persist_launch<k_persist_wide_gen<1, false>>(lb, a, s);
+        return a.dbg.out ? persist_launch<k_persist_wide_gen<1, RING, true>>(lb, a, s)
+                         : persist_launch<k_persist_wide_gen<1, RING, false>>(lb, a, s);
     }
     if (a.mode == 2) {
         if (a.cpw != 16 || a.n_classes != 2) return hipErrorInvalidValue;
-        return a.dbg.out ? persist_launch<k_persist_wide_gen<2, true>>(lb, a, s)
-                         : persist_launch<k_persist_wide_gen<2, false>>(lb, a, s);
+        return a.dbg.out ? persist_launch<k_persist_wide_gen<2, RING, true>>(lb, a, s)
+                         : persist_launch<k_persist_wide_gen<2, RING, false>>(lb, a, s);
     }
     if (a.mode != 0 || (a.n_classes != 512 && a.n_classes != 1024) || a.cpw * kPM != a.n_classes)
         return hipErrorInvalidValue;
-    return a.dbg.out ? persist_launch<k_persist_wide_gen<0, true>>(lb, a, s)
-                     : persist_launch<k_persist_wide_gen<0, false>>(lb, a, s);
+    return a.dbg.out ? persist_launch<k_persist_wide_gen<0, RING, true>>(lb, a, s)
+                     : persist_launch<k_persist_wide_gen<0, RING, false>>(lb, a, s);
+}
+}  // namespace
+hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s) {
+    return wide_gen_launch<false>(a, s);
+}
+// ring launch: P1 is formed from the per-frame tables and no stream is read, so the tables must
+// all be there; the instances must run without scratch
+hipError_t launch_persist_wide_gen_ring(const PersistGenRingArgs& a, hipStream_t s) {
+    if (!a.p1q || !a.p1a || !a.p1taps || a.hop <= 0 || a.p1split < 0 || a.mode < 0 || a.mode > 2 ||
+        persist_wide_gen_ring_scratch(a.mode) != 0)
+        return hipErrorInvalidValue;
+    return wide_gen_launch<true>(a, s);
 }
 
 // Exhaustive host check of the exchange layout (as wide_rr_layout_check): for every row count,

@@ -231,6 +231,8 @@ struct wrnn_handle {
     bool melup_valid = false;  // ws.melup holds the last call's upsampled mel (not per-frame P1)
     bool p1_ring = false;      // this call's k_persist launches form P1 in-kernel
     bool p1_stream = false;    // this call writes the [S][B][4H] P1 stream (other kernels)
+    bool gen_ring = false;     // geneing: every launch is wide and forms P1 / the noise in-kernel
+    double last_p1_bytes = 0, last_noise_bytes = 0;  // the per-step streams of the last call (wrnn_stream_info)
     bool sparse_call = false;  // this call's k_persist launches run the sparse instances
     PlanRates rates;           // per-step rates of the launch planner (load_rates, §3.0h)
     bool timing = false;
@@ -2218,8 +2220,9 @@ int persist_noise(wrnn_handle* h, int S, hipStream_t st) {
         any_reg |= !L.wide;
     }
     // (a rotated plan has only register-resident launches over the same rows: any_wide false)
-    // (the geneing wide kernel reads the stream like k_persist_gen: the whole stream below)
-    const bool ring_noise = any_wide && !h->pw.gen;
+    // (the geneing wide kernel's stream instances read the stream like k_persist_gen: the whole
+    // stream below; its ring instances, in calls of wide launches only, draw in-kernel)
+    const bool ring_noise = any_wide && (!h->pw.gen || h->gen_ring);
     if (raw && ring_noise && !any_reg) {  // every launch draws its noise in-kernel
         CHECK(P.gumbel.alloc(sizeof(float)));
         return WRNN_OK;
@@ -2548,7 +2551,19 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
                 // classes per slot of the wide layout (BITS: every class owned, n = 32 cpw; MOL /
                 // Beta: one tile of 16 in slots 0 and 1)
                 aw.cpw = a.mode == WRNN_MODE_RAW ? n / kPM : 16;
-                le = launch_persist_wide_gen(aw, st);
+                if (h->gen_ring) {  // the ring instances form P1 (BITS: and the noise) in-kernel
+                    PersistGenRingArgs awr{};
+                    static_cast<PersistGenArgs&>(awr) = aw;
+                    awr.p1q = ws.q4.f();
+                    awr.p1a = ws.a4.f();
+                    awr.p1taps = W.p1taps + (size_t)h->hop * 8;  // the [hop][4] table
+                    awr.p1split = W.p1split;
+                    le = launch_persist_wide_gen_ring(awr, st);
+                } else {
+                    le = launch_persist_wide_gen(aw, st);
+                }
+            } else if (h->gen_ring) {  // (plan_streams: the ring only in calls of wide launches)
+                return fail(WRNN_ERR_INVALID, "register-resident launch in a call without P1 / noise streams");
             } else {
                 le = launch_persist_gen(ag, st);
             }
@@ -3104,6 +3119,60 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
     }
 }
 
+// The per-step streams a planned call writes before its launches, and whether the workspace check
+// admits the persistent engine. One function for generate_impl (which sets p1_stream / gen_ring
+// from it), wrnn_stream_info and wrnn_debug_stream_bytes, so the three cannot drift.
+//   P1:    [S][Bp][np] floats unless every launch forms P1 in-kernel (fatchord ring, runtimeracer
+//          and geneing calls of wide launches only); then step 0 alone is formed: 0 bytes
+//   noise: the extent of the [S][Bp][n] Gumbel (RAW) or [S][Bp][kMolNoise] MOL stream; 0 when every
+//          launch draws in-kernel (Beta; RAW calls of in-kernel-noise wide launches only)
+// geneing ring (gen_frames: the per-frame P1 form exists and the ring instances run spill-free):
+// only calls whose launches are all wide, never time-sliced. sw = WRNN_GEN_RING: 1 the ring where
+// possible, 0 the streams, -1 the default -- the ring when the streams would not fit the
+// workspace cap, or when the head's measured call time is not above the stream form's
+// (kGenRingDefault).
+// The cap: fatchord and runtimeracer keep the whole-call bound S Bp (4 H + n) 4 bytes whatever
+// they write; geneing counts the streams the call really writes (P1 with its cI column).
+constexpr bool kGenRingDefault[3] = {true, true, true};  // BITS, MOL, Beta
+struct StreamPlan {
+    double p1_bytes = 0, noise_bytes = 0;
+    bool p1_stream = true, gen_ring = false, persist_ok = false;
+};
+StreamPlan plan_streams(const PlanIn& in, const PlanOut& out, bool p1x4, bool gen_frames, int sw) {
+    StreamPlan sp;
+    const int H = in.fat ? kPH : kRH;
+    const double rows_steps = (double)in.S * out.Bplan;
+    bool any_wide = false, any_reg = false;
+    for (const auto& L : out.lplan) {
+        any_wide |= L.wide;
+        any_reg |= !L.wide;
+    }
+    const bool all_wide = any_wide && !any_reg;
+    const bool raw = in.mode == WRNN_MODE_RAW;
+    sp.p1_stream = !out.p1_ring;
+    if (in.rr && in.rr_frames && all_wide) sp.p1_stream = false;  // runtimeracer: only wide launches
+    const double p1_full = rows_steps * (p1x4 ? 4 : 3) * H * 4.0;
+    const double noise_unit = in.mode == WRNN_MODE_BETA ? 0.0 : raw ? in.n * 4.0 : kMolNoise * 4.0;
+    // (persist_noise: RAW calls of fatchord / runtimeracer wide launches only draw in-kernel)
+    double noise = raw && all_wide && !in.gen ? 0.0 : rows_steps * noise_unit;
+    if (in.gen) {
+        const double cap_p1 = rows_steps * 4 * H * 4.0;  // (P1 and cI: 4 H floats either way)
+        const bool streams_fit = cap_p1 + noise <= kPersistWsBytes;
+        const bool can = gen_frames && all_wide && out.wrot.empty() && in.mode >= 0 && in.mode <= 2;
+        sp.gen_ring = can && sw != 0 && (sw == 1 || !streams_fit || kGenRingDefault[in.mode]);
+        if (sp.gen_ring) {
+            sp.p1_stream = false;
+            if (raw) noise = 0.0;  // (MOL keeps its k_mol_noise stream)
+        }
+        sp.persist_ok = (sp.gen_ring ? 0.0 : cap_p1) + noise <= kPersistWsBytes;
+    } else {
+        sp.persist_ok = rows_steps * (4 * H + in.n) * 4.0 <= kPersistWsBytes;
+    }
+    sp.p1_bytes = sp.p1_stream ? p1_full : 0.0;
+    sp.noise_bytes = noise;
+    return sp;
+}
+
 // PlanIn of a call on this handle: variant scratch from the device code objects, env switches.
 PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
     PlanIn in;
@@ -3240,16 +3309,27 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
     // PERSIST launch plan (plan_call): register-resident and wide launches by the rates of
     // h->rates, then time-sliced wide launches or a row rotation
     PlanOut pout;
-    plan_call(plan_inputs(h, B, S), h->rates, pout);
+    const PlanIn pin = plan_inputs(h, B, S);
+    plan_call(pin, h->rates, pout);
     const auto& lplan = pout.lplan;
     const int Bplan = pout.Bplan;
+    // geneing: the wide launches' ring instances (P1 and the BITS noise formed in-kernel) need the
+    // per-frame P1 form, spill-free instances and frame tables inside one 2-GiB buffer range.
+    // WRNN_GEN_RING=0|1 (read per call) forces the streams / the ring where it is possible
+    int gen_ring_sw = -1;
+    if (const char* env = std::getenv("WRNN_GEN_RING")) gen_ring_sw = std::atoi(env) != 0 ? 1 : 0;
+    const bool gen_frames = h->pw.ok && h->pw.gen && h->pw.wwide_gen && h->pw.p1x4 && h->pw.p1taps_ok &&
+                            h->pw.p1split >= 0 && p1_frames_enabled() &&
+                            persist_wide_gen_ring_scratch(h->cfg.mode) == 0 &&
+                            (double)(Fr + 1) * 4 * h->H * sizeof(float) < 2147483648.0;
+    const StreamPlan splan = plan_streams(pin, pout, h->pw.p1x4, gen_frames, gen_ring_sw);
     bool use_p = false;
     if (want != WRNN_ENGINE_CHAIN) {
         if (!h->pw.ok)
             why = "model is not fatchord (512 / 512), runtimeracer (256 / 256) or geneing (256 / 128) "
                   "with <= 1024 classes";
         else if (lplan.empty()) why = "no register-resident variant for this class count";
-        else if ((double)S * Bplan * (4 * h->H + h->n_classes) * 4.0 > kPersistWsBytes)
+        else if (!splan.persist_ok)  // (plan_streams: the streams this call would write)
             why = "P1 / noise workspace for " + std::to_string(B) + " rows x " + std::to_string(S) +
                   " steps exceeds " + std::to_string((long long)(kPersistWsBytes / (1 << 30))) + " GiB";
         else if (h->persist_failed && want != WRNN_ENGINE_PERSIST)
@@ -3269,12 +3349,12 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
     // per-frame form exists; the [S][B][4H] stream is written only for the other kernels
     h->p1_ring = use_p && pout.p1_ring;
     h->sparse_call = use_p && pout.sparse;
-    h->p1_stream = use_p && !h->p1_ring;  // (the wide launches form P1 in-kernel too)
-    if (h->p1_stream && h->pw.rr && rr_frames_ok(h)) {  // runtimeracer: only wide launches
-        bool all_wide = !h->p_plan.empty();                // form P1 in-kernel
-        for (const auto& L : h->p_plan) all_wide &= L.wide;
-        if (all_wide) h->p1_stream = false;
-    }
+    // (the fatchord wide launches form P1 in-kernel too; runtimeracer and geneing: calls of wide
+    // launches only -- plan_streams)
+    h->p1_stream = use_p && splan.p1_stream;
+    h->gen_ring = use_p && splan.gen_ring;
+    h->last_p1_bytes = use_p ? splan.p1_bytes : 0.0;
+    h->last_noise_bytes = use_p ? splan.noise_bytes : 0.0;
     // MelResNet frame columns: utterance u at [col0[u], col0[u] + T[u])
     std::vector<int> Ts(n_utts), col0(n_utts);
     int Tsum = 0;
@@ -3357,6 +3437,7 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
             std::fprintf(stderr, "[wavernn-mi355x] WARNING: persist engine failed (%s); this call runs on the "
                                  "chain engine (~14x slower)\n", g_err.c_str());
             use_p = false;
+            h->last_p1_bytes = h->last_noise_bytes = 0.0;  // (wrnn_stream_info: 0 after a CHAIN call)
             if (h->pw.p1x4)  // cI was not written (P1 carried it): conditioning again, cI only
                 for (int u = 0; u < n_utts; ++u)
                     CHECK(run_upsample(h, mels[u], plan[u].T, plan[u].B, batched ? target + overlap : 0,
@@ -3880,19 +3961,15 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap) {
 }
 
 constexpr int kPlanRowsMax = 1 << 20;  // wrnn_debug_plan: far above any call (C4 is 144 rows per GPU)
-int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
-                    int* n_launches, int* rows_per_group, int* wide, int cap, int* rot_launches) {
-    if (!n_launches || !rot_launches) return fail(WRNN_ERR_INVALID, "null argument");
-    if (rows < 1 || seq_len < 1 || cap < 0) return fail(WRNN_ERR_INVALID, "bad arguments");
+// PlanIn of a described call (wrnn_debug_plan, wrnn_debug_stream_bytes): every variant spill-free
+static int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_len, int flags, PlanIn& in) {
+    if (rows < 1 || seq_len < 1) return fail(WRNN_ERR_INVALID, "bad arguments");
     // (1 << bits below; the planner's tables have rows + 1 entries)
     if (bits < 1 || bits > 10) return fail(WRNN_ERR_INVALID, "bits must be 1..10");
     if (mode != WRNN_MODE_RAW && mode != WRNN_MODE_MOL && mode != WRNN_MODE_BETA)
         return fail(WRNN_ERR_INVALID, "mode must be one of WRNN_MODE_*");
     if (rows > kPlanRowsMax) return fail(WRNN_ERR_INVALID, "rows above " + std::to_string(kPlanRowsMax));
-    PlanRates R;
-    std::string err;
-    if (table && !parse_rates(table, R, err)) return fail(WRNN_ERR_INVALID, "rate table: " + err);
-    PlanIn in;
+    in = PlanIn();
     in.ok = true;
     in.fat = model_type == WRNN_MODEL_FATCHORD;
     in.rr = model_type == WRNN_MODEL_RUNTIMERACER;
@@ -3907,7 +3984,8 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     // flags: 1 sparse image, 2 P1 ring / per-frame P1 (fatchord, runtimeracer), 4 wide images
     // (fatchord RAW / MOL, runtimeracer RAW, geneing BITS with 512 or 1024 classes), 16 the
     // runtimeracer MOL wide image, 32 the geneing MOL wide image, 64 the geneing Beta wide image;
-    // every variant spill-free
+    // every variant spill-free. (128, geneing in-kernel conditioning, does not enter the plan:
+    // wrnn_debug_stream_bytes)
     in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.force_sp = in.sp && (flags & 8);
     in.p1ring = in.fat && (flags & 2);
@@ -3919,6 +3997,18 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     in.has_wide_gen_mol = in.gen && (flags & 32) && mode == WRNN_MODE_MOL;
     in.has_wide_gen_beta = in.gen && (flags & 64) && mode == WRNN_MODE_BETA;
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
+    return WRNN_OK;
+}
+
+int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
+                    int* n_launches, int* rows_per_group, int* wide, int cap, int* rot_launches) {
+    if (!n_launches || !rot_launches) return fail(WRNN_ERR_INVALID, "null argument");
+    if (cap < 0) return fail(WRNN_ERR_INVALID, "bad arguments");
+    PlanRates R;
+    std::string err;
+    PlanIn in;
+    CHECK(debug_plan_in(model_type, bits, mode, rows, seq_len, flags, in));
+    if (table && !parse_rates(table, R, err)) return fail(WRNN_ERR_INVALID, "rate table: " + err);
     PlanOut out;
     plan_call(in, R, out);
     *n_launches = (int)out.lplan.size();
@@ -3927,6 +4017,28 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
         if (rows_per_group) rows_per_group[i] = out.lplan[i].nr;
         if (wide) wide[i] = out.lplan[i].wide ? 1 : 0;
     }
+    return WRNN_OK;
+}
+
+int wrnn_debug_stream_bytes(int model_type, int bits, int mode, int rows, int seq_len, int flags,
+                            double* p1_bytes, double* noise_bytes, int* persist_ok) {
+    if (!p1_bytes || !noise_bytes || !persist_ok) return fail(WRNN_ERR_INVALID, "null argument");
+    PlanIn in;
+    CHECK(debug_plan_in(model_type, bits, mode, rows, seq_len, flags, in));
+    PlanOut out;
+    plan_call(in, PlanRates(), out);  // the shipped rates
+    // (the x4 P1 form of the shipped models; no switch: the default rule)
+    const StreamPlan sp = plan_streams(in, out, true, in.gen && (flags & 128), -1);
+    *p1_bytes = sp.p1_bytes;
+    *noise_bytes = sp.noise_bytes;
+    *persist_ok = !out.lplan.empty() && sp.persist_ok ? 1 : 0;
+    return WRNN_OK;
+}
+
+int wrnn_stream_info(wrnn_handle* h, uint64_t* p1_bytes, uint64_t* noise_bytes) {
+    if (!h || !p1_bytes || !noise_bytes) return fail(WRNN_ERR_INVALID, "null argument");
+    *p1_bytes = (uint64_t)h->last_p1_bytes;
+    *noise_bytes = (uint64_t)h->last_noise_bytes;
     return WRNN_OK;
 }
 

@@ -399,6 +399,16 @@ struct PersistGenArgs {
     // wide-row launches (kernels_persist_wide_gen.hip): MFMA A-operand weight image
     const float4* wwide;    // [kPM][8 waves][8 float4][64 lanes]
 };
+// Ring launches of the wide kernel (launch_persist_wide_gen_ring): P1's per-frame form behind the
+// common arguments (as PersistArgs::p1q ..). The ring instances form P1 and (BITS) the Gumbel
+// noise in-kernel and read neither stream; `P1` then holds step 0 only (k_persist_gen_init).
+// (A struct of its own: the kernel arguments of every other geneing instance stay as they are.)
+struct PersistGenRingArgs : PersistGenArgs {
+    const float* p1q;       // [frame slots][4H]: M1_mel mel(frame), slot fbase = zero frame
+    const float* p1a;       // [frame slots][4H]: M1_aux aux(frame) + bP1 (zero frame: bP1)
+    const float* p1taps;    // [hop][4]
+    int p1split;
+};
 
 hipError_t launch_persist_gen(const PersistGenArgs& a, hipStream_t s);
 // Wide-row geneing launch (kernels_persist_wide_gen.hip): up to kPWideRows rows per XCD group,
@@ -407,11 +417,13 @@ hipError_t launch_persist_gen(const PersistGenArgs& a, hipStream_t s);
 // 2; cpw = 16: one fc3 tile in slots 0 and 1, the logits exchanged as tagged pairs in the
 // candidate area). Dispatches on a.mode.
 hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s);
+hipError_t launch_persist_wide_gen_ring(const PersistGenRingArgs& a, hipStream_t s);
 size_t persist_wide_gen_lds_bytes();
 size_t persist_wide_gen_xbuf_floats();
 size_t persist_wide_gen_wreg_floats();
 hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s);
-int persist_wide_gen_scratch(int mode);  // scratch bytes of the mode's instances (0 BITS, 1 MOL, 2 BETA)
+int persist_wide_gen_scratch(int mode);  // scratch bytes of the mode's stream instances (0 BITS, 1 MOL, 2 BETA)
+int persist_wide_gen_ring_scratch(int mode);  // ... of its ring instances (a ring launch needs 0)
 int wide_gen_layout_check(int rows_per_group);
 // host: violations of the MOL (30) / BETA (2) logit-pair layout; -1 for bad arguments
 int wide_gen_mol_layout_check(int rows_per_group, int n_logits);

@@ -42,6 +42,7 @@ EXPORTED = [
     'wrnn_set_utt_streams', 'wrnn_set_fold_ranges', 'wrnn_set_debug_steps', 'wrnn_debug_logits', 'wrnn_debug_wide_layout',
     'wrnn_debug_wide_mol_layout', 'wrnn_debug_wide_gen_layout', 'wrnn_debug_wide_rr_mol_layout',
     'wrnn_debug_wide_gen_mol_layout', 'wrnn_sparse_info', 'wrnn_set_rates', 'wrnn_get_rates', 'wrnn_debug_plan',
+    'wrnn_stream_info', 'wrnn_debug_stream_bytes',
 ]
 
 
@@ -138,6 +139,9 @@ def load_library(path=None):
         'wrnn_get_rates': (c_int, [c_void_p, ctypes.c_char_p, c_size_t]),
         'wrnn_debug_plan': (c_int, [ctypes.c_char_p, c_int, c_int, c_int, c_int, c_int, c_int, P(c_int),
                                     P(c_int), P(c_int), c_int, P(c_int)]),
+        'wrnn_stream_info': (c_int, [c_void_p, P(ctypes.c_uint64), P(ctypes.c_uint64)]),
+        'wrnn_debug_stream_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P(ctypes.c_double),
+                                            P(ctypes.c_double), P(c_int)]),
         'wrnn_debug_beta': (c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                     ctypes.c_uint32, ctypes.c_float, ctypes.c_float,
                                     P(ctypes.c_float)]),

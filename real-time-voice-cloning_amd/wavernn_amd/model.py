@@ -224,6 +224,14 @@ class WaveRNN:
         _abi.check(self._lib.wrnn_plan_info(self._h, ctypes.byref(n), fr, nr, wd, cap))
         return [(fr[i], nr[i], bool(wd[i])) for i in range(min(n.value, cap))]
 
+    def stream_info(self):
+        """(p1_bytes, noise_bytes): the per-step P1 and noise streams the last call wrote to
+        device memory before its launches; 0 where every launch formed them in-kernel (a geneing
+        call of wide launches only: both; env WRNN_GEN_RING=0 keeps its streams)."""
+        p1, nz = ctypes.c_uint64(), ctypes.c_uint64()
+        _abi.check(self._lib.wrnn_stream_info(self._h, ctypes.byref(p1), ctypes.byref(nz)))
+        return p1.value, nz.value
+
     def rot_info(self):
         """Row rotation of the last persistent call: (launches, steps per
         launch of the q + 1-row groups, of the q-row groups); (0, 0, 0) when none."""
