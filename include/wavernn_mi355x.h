@@ -194,6 +194,14 @@ int wrnn_generate_batch_device(wrnn_handle* h, int n_utts, const float* const* m
 /* Select the recurrence engine for later calls (WRNN_ENGINE_*). Requesting PERSIST for a
  * call that does not qualify makes that call fail with WRNN_ERR_INVALID. */
 int wrnn_set_engine(wrnn_handle* h, int engine);
+/* Row capacity per XCD group of the geneing wide launches (operator tuning; no reference
+ * equivalent): 16 (the default) or 32. With 32, a call whose launches are all
+ * wide and that forms its conditioning in-kernel may run launches of 17 .. 32 rows per group on the
+ * 32-row instances of the wide kernel (rate keys wide_gen32, wide_gen32_mol, wide_gen32_beta);
+ * results equal the 16-row launches' bit for bit. Any other value, or 32 on a handle that is not
+ * geneing, is WRNN_ERR_INVALID. Env WRNN_GEN_WIDE_ROWS=16|32 (read per call) overrides the handle's
+ * setting; under WRNN_GEN_RING=0 no 32-row launch is planned. */
+int wrnn_set_gen_wide_rows(wrnn_handle* h, int rows);
 /* Engine that ran the last call. */
 int wrnn_last_engine(wrnn_handle* h, int* engine);
 /* Calls on this handle that fell back from PERSIST to CHAIN under WRNN_ENGINE_AUTO (the
@@ -226,7 +234,10 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap);
  * plan none unless forced), 8 sparse forced (WRNN_SPARSE=1), 16 runtimeracer MOL wide image (flag 4
  * does not cover it; priced by the rate key wide_rr_mol, and planned only for calls of more than
  * 32 rows), 32 geneing MOL wide image, 64 geneing Beta wide image (rate keys wide_gen_mol /
- * wide_gen_beta, likewise only for calls of more than 32 rows). bits outside 1..10, an unknown mode or more than 2^20 rows are
+ * wide_gen_beta, likewise only for calls of more than 32 rows), 256 the geneing 32-row ring instances
+ * are available and selected (wrnn_set_gen_wide_rows(32); needs flag 128 of wrnn_debug_stream_bytes
+ * and the head's flag 4 / 32 / 64; rate keys wide_gen32, wide_gen32_mol, wide_gen32_beta; only in
+ * plans whose launches are all wide). bits outside 1..10, an unknown mode or more than 2^20 rows are
  * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag of the first `cap`,
  * and the row rotation's launch count (0: none). */
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
@@ -354,6 +365,13 @@ int wrnn_debug_wide_gen_layout(int rows_per_group);
  * that (row, logit), the area disjoint from the vector slots -- or WRNN_ERR_INVALID (also for any
  * other n_logits). No device needed. */
 int wrnn_debug_wide_gen_mol_layout(int rows_per_group, int n_logits);
+/* The same two checks for the 32-row instances of the geneing wide launch (1..32 rows per group;
+ * rows 16..31 are a second column tile with its own copy of the group's exchange area): each
+ * tile's layout as above, every producer packet meeting its consumer through the kernel's row ->
+ * (tile, column) mapping at absolute offsets of the doubled area, and the two copies disjoint.
+ * Violations, or WRNN_ERR_INVALID. No device needed. */
+int wrnn_debug_wide_gen32_layout(int rows_per_group);
+int wrnn_debug_wide_gen32_mol_layout(int rows_per_group, int n_logits);
 
 /* Raw access for tests: copy the RAW noise (seq_len, rows, n_classes) of the last call's
  * first `n_steps` steps to host (float32). */

@@ -3,7 +3,9 @@
 // matrix cores (v_mfma_f32_16x16x4_f32). Three heads, each its own instantiation (template
 // parameter MODE): geneing 'BITS' (WRNN_MODE_RAW, 512 or 1024 classes), MOL (30 logits, mixture of
 // logistics) and Beta (geneing 'RAW', WRNN_MODE_BETA, 2 logits). Calls of at most 32 rows stay on
-// k_persist_gen (the planner offers this kernel above that, or under WRNN_PERSIST_WIDE=1).
+// k_persist_gen (the planner offers this kernel above that, or under WRNN_PERSIST_WIDE=1). The
+// 32-row ring instances (k_persist_wide_gen32, below the 16-row kernel: two column tiles per group,
+// 256 rows per launch) are opt-in (wrnn_set_gen_wide_rows).
 //
 // Reference step body: vocoder/models/geneing_version.py:193-205 (rnn_dims 256, fc_dims 128):
 //   x1 = I(x0) + h1'     h1' = rnn1(I(x0), h1)
@@ -180,16 +182,19 @@ __device__ __forceinline__ bool g_poll(rsrc_t xr, unsigned voff, unsigned so, bo
 // The Gumbel word of (tau, row n, class) as k_gumbel forms it (philox.h gumbel_q_of, keyed by
 // class quad, absolute step, fold, stream). Thread j of a row takes class j of slot w (cpw 16,
 // ntc 1) or the pair 2 j, 2 j + 1 (cpw 32, ntc 2: one Philox block for both).
+// (LRI, LGR / LP1: the LDS offsets of the RowInfo array and of the destination array -- the 32-row
+// instances, whose arrays lie elsewhere, run the same code)
+template <int LRI = WL_RI, int LGR = WL_GR>
 __device__ __forceinline__ void ring_noise_make(const PersistGenRingArgs& a, float* lds, int w, int ntc, int n,
                                                 int j, int tau) {
     int c = a.cpw * w + (ntc == 2 ? 2 * j : j);
     asm volatile("" : "+v"(c));
-    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[n];
+    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + LRI)[n];
     // (a padding row repeats the last real row: drawn and never used)
     const U4 o = philox4x32_10((uint32_t)(c >> 2), (uint32_t)tau, (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
     const int q = c & 3;
     const uint32_t wd = q == 0 ? o.x : q == 1 ? o.y : q == 2 ? o.z : o.w;
-    float* dst = lds + WL_GR + n * kGrW + (ntc == 2 ? 2 * j : j);
+    float* dst = lds + LGR + n * kGrW + (ntc == 2 ? 2 * j : j);
     dst[0] = __uint_as_float(gumbel_q_of(wd));
     if (ntc == 2) {  // class c + 1 of the same quad (c is even)
         __builtin_amdgcn_sched_barrier(0);
@@ -200,11 +205,12 @@ __device__ __forceinline__ void ring_noise_make(const PersistGenRingArgs& a, flo
 // zero tap (as kernels_persist_wide.hip p1_make): positions >= L take the zero frame at fbase
 // (bias only), frames outside the utterance its zeroed guard slots; tau is clamped at the row's
 // last step, as the stream read clamps it.
+template <int LRI = WL_RI, int LP1 = WL_P1R>
 __device__ __forceinline__ void ring_p1_make(const PersistGenRingArgs& a, float* lds, int w, int n, int j, int tau) {
     const int tc = tau < a.S ? tau : a.S - 1;
     int uu = GU * w + j;
     asm volatile("" : "+v"(uu));
-    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[n];
+    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + LRI)[n];
     const unsigned p = (unsigned)(ri.rel0 + tc);
     const bool in = p < (unsigned)ri.L;  // else the zero tail pad: bias only (zero frame)
     const unsigned f = p / (unsigned)a.hop, sph = in ? p - f * (unsigned)a.hop : 0u;
@@ -231,10 +237,9 @@ __device__ __forceinline__ void ring_p1_make(const PersistGenRingArgs& a, float*
         m.z = fmaf(kk[k], tq[k].z, m.z);
         m.w = fmaf(kk[k], tq[k].w, m.w);
     }
-    reinterpret_cast<float4*>(lds + WL_P1R)[n * GU + j] =
+    reinterpret_cast<float4*>(lds + LP1)[n * GU + j] =
         make_float4(p_add(m.x, ta.x), p_add(m.y, ta.y), p_add(m.z, ta.z), p_add(m.w, ta.w));
 }
-
 }  // namespace
 
 // MODE: 0 BITS (categorical), 1 MOL, 2 BETA (geneing 'RAW'); each its own instantiation (the BETA
@@ -650,6 +655,516 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(
     if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
 }
 
+// ---- 32-row ring instances ------------------------------------------------------------------
+// Up to 32 rows per XCD group in one launch: rows 0-15 of a group are MFMA column tile 0, rows
+// 16-31 column tile 1. Every wave polls both tiles' B-operand packets and runs each product for
+// both tiles on the same weight registers (two independent accumulator chains); the epilogue
+// cells of tile 0 lie on waves 0-3, those of tile 1 on waves 4-7, one cell per lane in the
+// (cn, cul) layout of a tile. A row's arithmetic is the 16-row ring instance's: the same weight
+// registers, the same K split over the 8 waves, the same fixed-order sum of the 8 partials, the
+// same epilogue, ring_p1_make / ring_noise_make and sampling code, so its outputs are the
+// 16-row instance's bit for bit. Ring form only (no stream instance).
+//
+// Exchange: tile 1 has its own copy of the whole per-group area (x1 / h1 / y1 parity slots and the
+// candidate / logit-pair area) kTile1B bytes behind tile 0's, so the offset functions above serve
+// both tiles; a group's area is 2 GX_GROUP floats. LDS: the partial buffers, the ring arrays and
+// the RowInfo array are twice the 16-row kernel's (W2_*).
+//
+// Ring work: waves 4-7 have no free tail here, so each wave set forms its own tile's next noise /
+// P1 in two parts. At the top of a step, before the hop-1 poll, a thread issues the table loads of
+// its P1 cell (their addresses depend only on t and the row; in flight over the whole step) and
+// forms the Philox words and the first Gumbel word of its noise cell in the wait for x1. After it
+// has published its fc3 candidates (logits) and before it polls the candidates of hop 3 -- in the
+// flight time of that exchange -- it forms the second Gumbel word and the P1 value and writes both
+// cells. The order is kept by the same two barriers: the arrays are read after a step's first
+// barrier and written after its second.
+namespace {
+constexpr int kRows32 = 2 * kRowsW;
+constexpr unsigned kTile1B = (unsigned)GX_GROUP * 4u;  // byte offset of tile 1's copy in a group's area
+constexpr int GX_GROUP32 = 2 * GX_GROUP;
+constexpr int W2_RI = 0;  // RowInfo of the group's rows (6 words each)
+constexpr int W2_FAIL = kRows32 * 6, W2_REG = W2_FAIL + 4, W2_CB = W2_REG + 12;
+constexpr int W2_P = 512;  // partial tiles [tile][8 v][nt][16 n][16 m], one buffer per product
+constexpr int W2P_F1 = W2_P, W2P_HH = W2P_F1 + 2 * WT, W2P_F3 = W2P_HH + 4 * WT;
+constexpr int W2_P1R = W2P_F3 + 4 * WT, W2_GR = W2_P1R + kRows32 * GU * 4, W2_TOTAL = W2_GR + kRows32 * kGrW;
+static_assert(W2_CB + 32 + 32 <= W2_P && W2_REG % 4 == 0, "slot constants overflow");
+static_assert(W2_P % 4 == 0 && W2_P1R % 4 == 0 && WT % 4 == 0, "partial tiles and P1 array: float4-aligned");
+static_assert(W2_TOTAL * sizeof(float) <= 160 * 1024, "LDS of the 32-row instances exceeds 160 KiB");
+static_assert(kTile1B % 16 == 0, "tile 1's copy: 16-byte aligned");
+
+// ring_p1_make and ring_noise_make in two parts each, the same operations in the same order: the
+// 32-row instances issue a step's table loads and draw its Philox words at the top of the step
+// before, and form the values after that step's second barrier (k_persist_wide_gen32)
+struct RingP1Taps {
+    float4 tk, tq[4], ta;
+};
+__device__ __forceinline__ void ring_p1_load(const PersistGenRingArgs& a, const RowInfo& ri, int w, int j, int tau,
+                                             RingP1Taps& o) {
+    const int tc = tau < a.S ? tau : a.S - 1;
+    int uu = GU * w + j;
+    asm volatile("" : "+v"(uu));
+    const unsigned p = (unsigned)(ri.rel0 + tc);
+    const bool in = p < (unsigned)ri.L;  // else the zero tail pad: bias only (zero frame)
+    const unsigned f = p / (unsigned)a.hop, sph = in ? p - f * (unsigned)a.hop : 0u;
+    const unsigned s0 = in ? (unsigned)ri.fbase - 1u + f + (sph >= (unsigned)a.p1split ? 1u : 0u)
+                           : (unsigned)ri.fbase;
+    constexpr unsigned kRow = 4u * GH * 4u;  // bytes per frame slot
+    const unsigned col = (unsigned)uu * 16u;
+    o.tk = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(mk_rsrc(a.p1taps), sph * 16u, 0, 0));
+    const rsrc_t qr = mk_rsrc(a.p1q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        o.tq[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                 qr, (in ? s0 + (unsigned)k : s0) * kRow + col, 0, 0));
+    o.ta = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                          mk_rsrc(a.p1a), (in ? (unsigned)ri.fbase + 1u + f : s0) * kRow + col, 0, 0));
+}
+__device__ __forceinline__ float4 ring_p1_finish(const RingP1Taps& o) {
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float kk[4] = {o.tk.x, o.tk.y, o.tk.z, o.tk.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        m.x = fmaf(kk[k], o.tq[k].x, m.x);
+        m.y = fmaf(kk[k], o.tq[k].y, m.y);
+        m.z = fmaf(kk[k], o.tq[k].z, m.z);
+        m.w = fmaf(kk[k], o.tq[k].w, m.w);
+    }
+    return make_float4(p_add(m.x, o.ta.x), p_add(m.y, o.ta.y), p_add(m.z, o.ta.z), p_add(m.w, o.ta.w));
+}
+// the Philox words of the thread's class (wd) and, ntc 2, of class c + 1 of the same quad (wd1)
+__device__ __forceinline__ void ring_noise_words(const PersistGenRingArgs& a, const RowInfo& ri, int w, int ntc, int j,
+                                                 int tau, uint32_t& wd, uint32_t& wd1) {
+    int c = a.cpw * w + (ntc == 2 ? 2 * j : j);
+    asm volatile("" : "+v"(c));
+    const U4 o = philox4x32_10((uint32_t)(c >> 2), (uint32_t)tau, (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
+    const int q = c & 3;
+    wd = q == 0 ? o.x : q == 1 ? o.y : q == 2 ? o.z : o.w;
+    wd1 = q == 0 ? o.y : o.w;
+}
+
+// g_poll over both tiles: the lane's NP packets of tile 0 and of tile 1 (kTile1B behind) in one
+// pass, until none holds the sentinel; bounded and recorded exactly as g_poll
+template <int NP>
+__device__ __forceinline__ bool g_poll2(rsrc_t xr, unsigned voff, unsigned so, bool valid0, bool valid1,
+                                        u4v (&c0)[2], u4v (&c1)[2], unsigned* ctl, unsigned where, unsigned step) {
+    const unsigned t0 = p_now();
+    unsigned nsp = 0;
+    while (true) {
+        unsigned vo0 = valid0 ? voff : kNoOff, vo1 = valid1 ? voff : kNoOff;
+        asm volatile("" : "+v"(vo0), "+v"(vo1));
+        c0[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo0, so, kCpNT);
+        if constexpr (NP == 2) c0[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo0 + 1024u, so, kCpNT);
+        c1[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo1, so + kTile1B, kCpNT);
+        if constexpr (NP == 2) c1[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo1 + 1024u, so + kTile1B, kCpNT);
+        bool ok = g_ready(c0[0]);
+        ok &= g_ready(c1[0]);
+        if constexpr (NP == 2) {
+            ok &= g_ready(c0[1]);
+            ok &= g_ready(c1[1]);
+        }
+        if (__all((int)ok)) return true;
+        if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
+            if ((threadIdx.x & 63) == 0 && !ld_sc1_u(ctl + PC_ERR) &&
+                atomicCAS(ctl + PC_WHERE, 0u, where | ((threadIdx.x >> 6) << 19)) == 0u) {
+                ctl[PC_WHERE + 1] = 1u;
+                ctl[PC_WHERE + 2] = step;
+            }
+            if ((threadIdx.x & 63) == 0) atomicMax(ctl + PC_ERR, 2u);
+            return false;
+        }
+    }
+}
+
+}  // namespace
+
+template <int MODE, bool DBG>
+__global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen32(PersistGenRingArgs a) {
+    static_assert(MODE >= 0 && MODE <= 2, "BITS, MOL or BETA");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int* sreg = reinterpret_cast<int*>(lds + W2_REG);
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int gg, ss;
+        sreg[2] = p_register(a.ctl, gg, ss);
+        sreg[0] = gg;
+        sreg[1] = ss;
+    }
+    __syncthreads();
+    if (!sreg[2]) return;
+    const int g = __builtin_amdgcn_readfirstlane(sreg[0]);
+    const int w = __builtin_amdgcn_readfirstlane(sreg[1]);
+    const int v = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave: K-eighth v of every product
+    const int tt = v >> 2;                                   // ... and the tile of its epilogue cells
+    const int l = tid & 63;
+    const int R = a.nr;
+    const int g0 = a.rb + g;
+    const int bn = l & 15;
+    const bool bvalid0 = bn < R, bvalid1 = kRowsW + bn < R;
+    // epilogue cell (row cn of the group = column cnl of tile tt, tile row cul)
+    const int cn = tid >> 4, cnl = cn & 15, cul = tid & 15;
+    const bool cell = cn < R;
+    const bool gcell = cell && cul < GU;      // GRU cell: unit 8 w + cul
+    const bool fcell = cell && cul < GO;      // fc1 cell: output 4 w + cul
+    const int cu = GU * w + (cul & 7);
+    const int crow = g0 + kPG * (cell ? cn : 0);
+    const int ntc = MODE == 0 ? a.cpw / 16 : 1;  // fc3 tiles of the slot (1 or 2; MOL / BETA: 1)
+    const rsrc_t xr = mk_rsrc(a.xbuf + (size_t)g * GX_GROUP32);
+    const unsigned xt = (unsigned)tt * kTile1B;  // the cell's tile copy (uniform)
+    const unsigned o_cx = g_cons_x(v, l), o_cy = g_cons_y(v, l);
+    const unsigned o_px = gcell && (cul & 3) == 0 ? g_prod_x(GU * w + cul, cnl) : kNoOff;
+    const unsigned o_py = cell && cul == 0 ? g_prod_y(GO * w, cnl) : kNoOff;
+    auto wh = [&](unsigned site) { return site << 28 | (unsigned)w << 22; };
+
+    float4 wq[kWgq];  // (the 16-row kernel's image and register assignment)
+    {
+        const float4* src = a.wwide + ((size_t)(w * 8 + v) * kWgq) * 64 + l;
+#pragma unroll
+        for (int q = 0; q < kWgq; ++q) wq[q] = src[(size_t)q * 64];
+    }
+    const RowInfo* rinfo = reinterpret_cast<const RowInfo*>(lds + W2_RI);
+    if (tid < R) reinterpret_cast<RowInfo*>(lds + W2_RI)[tid] = a.rows[g0 + kPG * tid];
+    if (tid == 0) lds[W2_FAIL] = 0.f;
+    if (tid < 24) lds[W2_CB + tid] = a.b_hh1[(tid >> 3) * GH + GU * w + (tid & 7)];
+    if (tid >= 32 && tid < 32 + a.cpw) {
+        const int c = a.cpw * w + tid - 32;
+        lds[W2_CB + tid] = c < a.n_classes ? a.b_f3[c] : 0.f;
+    }
+
+    // (as the 16-row kernel's pub, into the cell's tile copy)
+    auto pub = [&](int buf, int sz, unsigned off, float val, unsigned seq) {
+        const float u1 = pdpp<0x39>(val), u2 = pdpp<0x4E>(val), u3 = pdpp<0x93>(val);
+        unsigned vo = off;
+        asm volatile("" : "+v"(vo));
+        __builtin_amdgcn_raw_buffer_store_b128(
+            (u4v){__float_as_uint(val), __float_as_uint(u1), __float_as_uint(u2), __float_as_uint(u3)}, xr, vo,
+            g_slot(buf, sz, seq) + xt, 0);
+        __builtin_amdgcn_raw_buffer_store_b128((u4v){kSentG, kSentG, kSentG, kSentG}, xr, vo,
+                                               g_slot(buf, sz, seq + 1u) + xt, 0);
+    };
+    // partial tile j of a product, column tile `tile`, into P ([tile][v][nt][n][m], swizzled)
+    auto put = [&](int P, int NT, int tile, int j, const v4f& acc) {
+        *reinterpret_cast<v4f*>(lds + P + tile * NT * WT + ((v * NT + j) * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc;
+    };
+    // the cell's sum of the 8 waves' partials of tile j, tile row m (fixed order v = 0 .. 7)
+    auto psum = [&](int P, int NT, int j, int m) {
+        float p[8];
+#pragma unroll
+        for (int vv = 0; vv < 8; ++vv)
+            p[vv] = lds[P + tt * NT * WT + ((vv * NT + j) * 16 + cnl) * 16 + wsw(cnl, m)];
+        float acc = 0.f;
+#pragma unroll
+        for (int vv = 0; vv < 8; ++vv) acc += p[vv];
+        return acc;
+    };
+
+    float h1r = 0.f, x1c = 0.f;
+    if (gcell) {  // x1, h1 of step 0 (k_persist_gen_init)
+        const float* st = a.st + (size_t)crow * 2 * GH;
+        x1c = st[cu];
+        h1r = st[GH + cu];
+    }
+    const float vr = gcell ? a.v[cu] : 0.f, vz = gcell ? a.v[GH + cu] : 0.f, vn = gcell ? a.v[2 * GH + cu] : 0.f;
+    const float w0c = gcell ? a.w0[cu] : 0.f;
+    const float* cb = lds + W2_CB;
+    const rsrc_t fcr = mk_rsrc(a.fcond);
+    const unsigned o_gn = (unsigned)(crow * kMolNoise + cul) * 4u;  // (MOL draw stream)
+    [[maybe_unused]] float pg = 0.f, pgn = 0.f;
+    [[maybe_unused]] auto mol_draw = [&](int te) {
+        const int tc = te < a.S ? te : a.S - 1;
+        if (cell && cul < kMolNoise) pgn = bld(mk_rsrc(a.gumbel + (size_t)tc * a.B * kMolNoise), o_gn, 0);
+    };
+    [[maybe_unused]] const bool l_ra = cell && cul < a.n_classes, l_rb = cell && 16 + cul < a.n_classes;
+    [[maybe_unused]] const unsigned o_lp =
+        cell && w < 2 && 16 * w + cul < a.n_classes ? g_logit(cnl, 16 * w + cul) : kNoOff;
+    // thread i of a wave set forms, for its tile, the P1 cell (row i / 8, unit i % 8) and, BITS, the
+    // noise cell (row i / 16, thread i % 16 of the row) of the rows below R
+    const int ri_ = tid & 255;
+    const int n1 = kRowsW * tt + (ri_ >> 3), n2 = kRowsW * tt + (ri_ >> 4);
+    const bool p1do = n1 < R, nzdo = MODE == 0 && n2 < R;
+    auto ring_make = [&](int t_noise, int t_p1) {  // (the prologue: both parts at once)
+        if (p1do) ring_p1_make<W2_RI, W2_P1R>(a, lds, w, n1, ri_ & 7, t_p1);
+        if constexpr (MODE == 0)
+            if (nzdo) ring_noise_make<W2_RI, W2_GR>(a, lds, w, ntc, n2, ri_ & 15, t_noise);
+    };
+    __syncthreads();
+    // ring prologue: the noise of step t0 and P1(t0 + 1), read after step t0's first barrier
+    ring_make(a.t0, a.t0 + 1);
+    if constexpr (MODE == 1) {
+        mol_draw(a.t0);
+        pg = pgn;
+    }
+    pub(GX_X1, GS_X, o_px, __builtin_canonicalizef(x1c), (unsigned)a.t0 + 1u);
+    pub(GX_H1, GS_X, o_px, __builtin_canonicalizef(h1r), (unsigned)a.t0 + 1u);
+    bool fail = false;
+    u4v c0[2], c1[2];
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[0] = p_now();
+    for (int t = a.t0; t < a.t1; ++t) {
+        const unsigned seq = (unsigned)t + 1u;
+        float pc = 0.f;
+        [[maybe_unused]] float pn[2] = {0.f, 0.f};
+        float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (fcell) pc = bld(fcr, (unsigned)(p_frame(rinfo[cn], t, a.hop) * a.cond_width + a.oF1 + GO * w + cul) * 4u, 0);
+        if constexpr (MODE == 1) mol_draw(t + 1);
+        // the thread's ring cells of the next step, first part: the table loads of P1(t + 2) are in
+        // flight over the whole step, the Philox words of step t + 1 and the first Gumbel word are
+        // formed in the wait for x1; the values go to LDS after the second barrier
+        RingP1Taps pt;
+        [[maybe_unused]] uint32_t nw0 = 0, nw1 = 0, ng0 = 0;
+        if (p1do) ring_p1_load(a, rinfo[n1], w, ri_ & 7, t + 2, pt);
+        if constexpr (MODE == 0) {
+            if (nzdo) {
+                ring_noise_words(a, rinfo[n2], w, ntc, ri_ & 15, t + 1, nw0, nw1);
+                ng0 = gumbel_q_of(nw0);
+            }
+            asm volatile("" : "+v"(ng0), "+v"(nw1));
+        }
+        // ---- hop 1: x1 of every slot, both tiles -> fc1 -> y1 --------------------------------
+        fail |= !g_poll2<2>(xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid0, bvalid1, c0, c1, a.ctl, wh(1), (unsigned)t);
+        {
+            v4f e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const float wa = f4c(wq[4 + ks / 4], ks % 4);
+                e0 = mfma4(wa, u4c(c0[ks >> 2], ks & 3), e0);
+                e1 = mfma4(wa, u4c(c1[ks >> 2], ks & 3), e1);
+            }
+            put(W2P_F1, 1, 0, 0, e0);
+            put(W2P_F1, 1, 1, 0, e1);
+        }
+        if (fail) lds[W2_FAIL] = 1.f;
+        gbar();
+        if (lds[W2_FAIL] != 0.f) return;
+        {
+            float y = 0.f;
+            if (fcell) {
+                y = p_add(psum(W2P_F1, 1, 0, cul), pc);
+                y = y > 0.f ? y : 0.f;
+            }
+            pub(GX_Y1, GS_Y, o_py, y, seq);
+            // the tile's noise of step t and P1(t + 1): written before the barrier above (step
+            // t - 1's epilogue, or the prologue), overwritten only after the barrier below
+            if constexpr (MODE == 0) {
+                if (cell) {
+                    pn[0] = lds[W2_GR + cn * kGrW + cul];
+                    if (ntc == 2) pn[1] = lds[W2_GR + cn * kGrW + 16 + cul];
+                }
+            }
+            if (gcell) pp = reinterpret_cast<const float4*>(lds + W2_P1R)[cn * GU + cul];
+        }
+        // ---- in the wait for y1: h1 of every slot -> W_hh1 h1 ---------------------------------
+        fail |= !g_poll2<2>(xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid0, bvalid1, c0, c1, a.ctl, wh(2), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+            v4f b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const float x0 = u4c(c0[ks >> 2], ks & 3), x1 = u4c(c1[ks >> 2], ks & 3);
+                const float wa = f4c(wq[ks / 4], ks % 4), wb = f4c(wq[2 + ks / 4], ks % 4);
+                a0 = mfma4(wa, x0, a0);
+                b0 = mfma4(wa, x1, b0);
+                a1 = mfma4(wb, x0, a1);
+                b1 = mfma4(wb, x1, b1);
+            }
+            put(W2P_HH, 2, 0, 0, a0);
+            put(W2P_HH, 2, 0, 1, a1);
+            put(W2P_HH, 2, 1, 0, b0);
+            put(W2P_HH, 2, 1, 1, b1);
+        }
+        // ---- hop 2: y1 of every slot -> fc3 -> the slot's candidate of every row ------------
+        fail |= !g_poll2<1>(xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid0, bvalid1, c0, c1, a.ctl, wh(3), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+            v4f b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const float x0 = u4c(c0[0], ks), x1 = u4c(c1[0], ks);
+                a0 = mfma4(f4c(wq[6], ks), x0, a0);
+                b0 = mfma4(f4c(wq[6], ks), x1, b0);
+                if (ntc == 2) {
+                    a1 = mfma4(f4c(wq[7], ks), x0, a1);
+                    b1 = mfma4(f4c(wq[7], ks), x1, b1);
+                }
+            }
+            put(W2P_F3, 2, 0, 0, a0);
+            put(W2P_F3, 2, 1, 0, b0);
+            if (ntc == 2) {
+                put(W2P_F3, 2, 0, 1, a1);
+                put(W2P_F3, 2, 1, 1, b1);
+            }
+        }
+        if (fail) lds[W2_FAIL] = 1.f;
+        gbar();
+        {
+            [[maybe_unused]] const unsigned want = key_tag(seq);
+            float g1r = 0.f, g1z = 0.f, g1n = 0.f;
+            if constexpr (MODE == 0) {
+                uint32_t kh = 0, kl = 0;
+                if (cell) {
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        if (j >= ntc) break;
+                        const int c = a.cpw * w + 16 * j + cul;
+                        const float lg = p_add(psum(W2P_F3, 2, j, cul), cb[32 + 16 * j + cul]);
+                        p_dbg_logit<DBG>(a.dbg, t, crow, c, a.B, a.n_classes, lg);
+                        const CandKey k = cand_key(lg, __float_as_uint(pn[j]), c);
+                        kmax_take(kh, kl, k.hi, k.lo);
+                    }
+                }
+                row16_kmax(kh, kl);
+                unsigned vo = cell && cul == 0 ? g_cand(cnl, w) : kNoOff;
+                asm volatile("" : "+v"(vo));
+                __builtin_amdgcn_raw_buffer_store_b64((u2v){kh, kl | want}, xr, vo, GX_D * 4 + xt, 0);
+            } else {
+                float lg = 0.f;
+                if (o_lp != kNoOff) {
+                    lg = p_add(psum(W2P_F3, 2, 0, cul), cb[32 + cul]);
+                    p_dbg_logit<DBG>(a.dbg, t, crow, 16 * w + cul, a.B, a.n_classes, lg);
+                }
+                unsigned vo = o_lp;
+                asm volatile("" : "+v"(vo));
+                __builtin_amdgcn_raw_buffer_store_b64((u2v){__float_as_uint(lg), seq}, xr, vo, GX_D * 4 + xt, 0);
+            }
+            if (gcell) {  // gh1 = W_hh1 h1 + b_hh1 of the cell's unit
+                g1r = p_add(psum(W2P_HH, 2, 0, cul), cb[cul]);
+                g1z = p_add(psum(W2P_HH, 2, 0, 8 + cul), cb[8 + cul]);
+                g1n = p_add(psum(W2P_HH, 2, 1, cul), cb[16 + cul]);
+            }
+            // second part, while the candidates travel: the tile's noise of step t + 1 and P1(t + 2)
+            if constexpr (MODE == 0) {
+                if (nzdo) {
+                    float* dst = lds + W2_GR + n2 * kGrW + (ntc == 2 ? 2 * (ri_ & 15) : (ri_ & 15));
+                    dst[0] = __uint_as_float(ng0);
+                    if (ntc == 2) dst[1] = __uint_as_float(gumbel_q_of(nw1));
+                }
+            }
+            if (p1do) reinterpret_cast<float4*>(lds + W2_P1R)[n1 * GU + (ri_ & 7)] = ring_p1_finish(pt);
+            // ---- hop 3: sample of step t ------------------------------------------------------
+            float x;
+            if constexpr (MODE == 0) {
+                u4v q = {0u, want, 0u, want};
+                const unsigned t0s = p_now();
+                unsigned nsp = 0;
+                while (true) {
+                    if (cell) {
+                        unsigned vo = g_cand(cnl, 2 * cul);
+                        asm volatile("" : "+v"(vo));
+                        q = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, GX_D * 4 + xt, kCpNT);
+                    }
+                    if (__all(((q.y & kKeyTagMask) == want) & ((q.w & kKeyTagMask) == want))) break;
+                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
+                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
+                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(4) | ((unsigned)v << 19)) == 0u) {
+                            a.ctl[PC_WHERE + 1] = 1u;
+                            a.ctl[PC_WHERE + 2] = (unsigned)t;
+                        }
+                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
+                        fail = true;
+                        break;
+                    }
+                }
+                uint32_t bh = cell ? q.x : 0u, bl = cell ? q.y : 0u;
+                kmax_take(bh, bl, cell ? q.z : 0u, cell ? q.w : 0u);
+                row16_kmax(bh, bl);
+                const int bi = key_cls(bl);
+                {
+#pragma clang fp contract(off)
+                    x = (2.0f * (float)bi) / (float)(a.n_classes - 1) - 1.0f;
+                }
+                if (w == 0 && cell && cul == 0) {
+                    int nn = cn;
+                    asm volatile("" : "+v"(nn));
+                    const unsigned ro = (unsigned)((g0 + kPG * nn) * a.ld);
+                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u,
+                                                          (unsigned)t * 2u, 0);
+                    bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
+                }
+            } else {
+                unsigned va = l_ra ? g_logit(cnl, cul) : kNoOff;
+                unsigned vb = l_rb ? g_logit(cnl, 16 + cul) : kNoOff;
+                asm volatile("" : "+v"(va), "+v"(vb));
+                u2v qa, qb;
+                const unsigned t0s = p_now();
+                unsigned nsp = 0;
+                while (true) {
+                    qa = __builtin_amdgcn_raw_buffer_load_b64(xr, va, GX_D * 4 + xt, kCpNT);
+                    qb = __builtin_amdgcn_raw_buffer_load_b64(xr, vb, GX_D * 4 + xt, kCpNT);
+                    if (__all((!l_ra | (qa.y == seq)) & (!l_rb | (qb.y == seq)))) break;
+                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
+                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
+                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(5) | ((unsigned)v << 19)) == 0u) {
+                            a.ctl[PC_WHERE + 1] = 1u;
+                            a.ctl[PC_WHERE + 2] = (unsigned)t;
+                        }
+                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
+                        fail = true;
+                        break;
+                    }
+                }
+                const float la = __uint_as_float(qa.x);
+                [[maybe_unused]] const float lb = __uint_as_float(qb.x);
+                const int base = l & 48;  // lane 0 of this lane's row
+                if constexpr (MODE == 2) {
+                    double gv = 0.0;
+                    if (cell && cul < 2) {
+                        const RowInfo& ri = rinfo[cn];
+                        gv = gamma_mt((double)expf(la), (uint32_t)cul, (uint32_t)t, (uint32_t)ri.fold, ri.stream,
+                                      a.k0, a.k1);
+                    }
+                    const double gy = __shfl(gv, base + 1);
+                    float xv = 0.f;
+                    {
+#pragma clang fp contract(off)
+                        const float sb = (float)(gv / (gv + gy));
+                        xv = 2.0f * sb - 1.0f;
+                    }
+                    x = __shfl(xv, base);
+                } else {
+                    float bv;
+                    {
+#pragma clang fp contract(off)
+                        bv = cul < 10 ? la - pg : -INFINITY;
+                    }
+                    int bi = cul < 10 ? cul : 0x7fffffff;
+                    row16_argmax(bv, bi);
+                    bi = bi < 10 ? bi : 0;
+                    const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
+                    const float mean = bi < 6 ? m0 : m1;
+                    float ls = __shfl(lb, base + 4 + bi);
+                    const float lu = __shfl(pg, base + 10);
+                    {
+#pragma clang fp contract(off)
+                        const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
+                        ls = ls < lsmin ? lsmin : ls;
+                        x = mean + expf(ls) * lu;
+                        x = x < -1.f ? -1.f : x;
+                        x = x > 1.f ? 1.f : x;
+                    }
+                    pg = pgn;
+                }
+                if (w == 0 && cell && cul == 0) {
+                    int nn = cn;
+                    asm volatile("" : "+v"(nn));
+                    bst(x, mk_rsrc(a.samples), (unsigned)((g0 + kPG * nn) * a.ld) * 4u, (unsigned)t * 4u);
+                }
+            }
+            if (fail) lds[W2_FAIL] = 1.f;  // seen by every wave at the next step's check
+            // ---- GRU1 of step t + 1 for the slot's units -> x1, h1 ---------------------------
+            float x1 = 0.f;
+            if (gcell) {
+                h1r = p_gru(fmaf(vr, x, pp.x), fmaf(vz, x, pp.y), fmaf(vn, x, pp.z), g1r, g1z, g1n, h1r);
+                x1 = p_add(fmaf(w0c, x, pp.w), h1r);
+            }
+            pub(GX_X1, GS_X, o_px, x1, seq + 1u);
+            pub(GX_H1, GS_X, o_px, h1r, seq + 1u);
+        }
+        if (w == 0 && tid == 0) {
+            if (g == 0) p_progress(a.progress, a.prog_base, t);
+            if (p_abort(a.ctl, a.progress, t)) lds[W2_FAIL] = 1.f;  // seen at the next step's check
+        }
+    }
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
+}
+
 // launch-side helpers --------------------------------------------------------------------
 // at least 96 KB so that no CU can take two workgroups of this (register-light) kernel: every
 // group must span 32 CUs
@@ -745,6 +1260,73 @@ hipError_t launch_persist_wide_gen_ring(const PersistGenRingArgs& a, hipStream_t
         persist_wide_gen_ring_scratch(a.mode) != 0)
         return hipErrorInvalidValue;
     return wide_gen_launch<true>(a, s);
+}
+
+// ---- 32-row ring instances: launch side ---------------------------------------------------
+size_t persist_wide_gen32_lds_bytes() {
+    const size_t need = (size_t)W2_TOTAL * sizeof(float);
+    return need > 96 * 1024 ? need : 96 * 1024;  // (one workgroup per CU, as above)
+}
+size_t persist_wide_gen32_xbuf_floats() { return (size_t)kPG * GX_GROUP32; }
+// before every 32-row launch: both tile copies of every group, vector slots to the sentinel, the
+// candidate / logit areas to 0
+__global__ __launch_bounds__(256) void k_wide_gen32_xbuf_reset(uint4* x) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)kPG * GX_GROUP32 / 4) return;
+    const unsigned f = (unsigned)((i * 4) % GX_GROUP);  // (a tile copy is GX_GROUP floats)
+    x[i] = f >= (unsigned)GX_D ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(kSentG, kSentG, kSentG, kSentG);
+}
+hipError_t persist_wide_gen32_reset_xbuf(float* xbuf, hipStream_t s) {
+    const unsigned n = (unsigned)((size_t)kPG * GX_GROUP32 / 4);
+    k_wide_gen32_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf));
+    return hipGetLastError();
+}
+// scratch bytes of the mode's 32-row instances (the larger of production and DBG), read from the
+// code objects once per mode; -1: no such instance
+int persist_wide_gen32_scratch(int mode) {
+    if (mode < 0 || mode > 2) return -1;
+    static int cached[3] = {-2, -2, -2};  // -2: not read yet
+    if (cached[mode] == -2) {
+        hipFuncAttributes fa, fd;
+        const void* f = mode == 2 ? (const void*)k_persist_wide_gen32<2, false>
+                      : mode == 1 ? (const void*)k_persist_wide_gen32<1, false>
+                                  : (const void*)k_persist_wide_gen32<0, false>;
+        const void* d = mode == 2 ? (const void*)k_persist_wide_gen32<2, true>
+                      : mode == 1 ? (const void*)k_persist_wide_gen32<1, true>
+                                  : (const void*)k_persist_wide_gen32<0, true>;
+        if (hipFuncGetAttributes(&fa, f) != hipSuccess || hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
+        cached[mode] = (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
+    }
+    return cached[mode];
+}
+// the scratch a 32-row launch of the mode may carry: none; Beta at most the 16-byte frame its
+// other instances are accepted with
+bool persist_wide_gen32_usable(int mode) {
+    const int sc = persist_wide_gen32_scratch(mode);
+    return sc >= 0 && sc <= (mode == 2 ? 16 : 0);
+}
+// whole launches of up to 32 rows per group (t0 = 0), heads as launch_persist_wide_gen_ring
+hipError_t launch_persist_wide_gen32_ring(const PersistGenRingArgs& a, hipStream_t s) {
+    if (!a.p1q || !a.p1a || !a.p1taps || a.hop <= 0 || a.p1split < 0 || a.mode < 0 || a.mode > 2 ||
+        !persist_wide_gen32_usable(a.mode))
+        return hipErrorInvalidValue;
+    if (a.rb < 0 || a.nr < 1 || a.nr > kRows32 || a.rb + kPG * a.nr > a.B || a.t0 != 0 || a.t1 != a.S ||
+        a.vmap != nullptr || a.wwide == nullptr)
+        return hipErrorInvalidValue;
+    const size_t lb = persist_wide_gen32_lds_bytes();
+    if (a.mode == 1) {  // (the draws come from the k_mol_noise stream)
+        if (a.cpw != 16 || a.n_classes != 30 || a.gumbel == nullptr) return hipErrorInvalidValue;
+        return a.dbg.out ? persist_launch<k_persist_wide_gen32<1, true>>(lb, a, s)
+                         : persist_launch<k_persist_wide_gen32<1, false>>(lb, a, s);
+    }
+    if (a.mode == 2) {
+        if (a.cpw != 16 || a.n_classes != 2) return hipErrorInvalidValue;
+        return a.dbg.out ? persist_launch<k_persist_wide_gen32<2, true>>(lb, a, s)
+                         : persist_launch<k_persist_wide_gen32<2, false>>(lb, a, s);
+    }
+    if ((a.n_classes != 512 && a.n_classes != 1024) || a.cpw * kPM != a.n_classes) return hipErrorInvalidValue;
+    return a.dbg.out ? persist_launch<k_persist_wide_gen32<0, true>>(lb, a, s)
+                     : persist_launch<k_persist_wide_gen32<0, false>>(lb, a, s);
 }
 
 // Exhaustive host check of the exchange layout (as wide_rr_layout_check): for every row count,
@@ -851,6 +1433,86 @@ int wide_gen_mol_layout_check(int R, int n_logits) {
             if (g_slot(bufs[b], szs[b], sq) + (unsigned)szs[b] * 4u > (unsigned)GX_D * 4u) ++bad;
     if (GX_D + area > GX_GROUP || GX_D % 2) ++bad;
     if ((unsigned long long)kNoOff + (unsigned long long)GX_D * 4ull + 8ull <= 0x7fffffffull) ++bad;
+    return bad;
+}
+
+// The 32-row instances' exchange layout for a group of R rows (1 .. 32): each tile's own layout by
+// the check above, then, with the kernel's own row -> (tile, column) mapping and absolute byte
+// offsets inside the group's area of 2 GX_GROUP floats, every producer packet of x1 / h1 / y1 (both
+// parity slots) meets exactly one consumer packet of the same (row, unit quad) and lies inside its
+// tile's copy, every candidate couple a lane polls lies in its tile's candidate area, the two
+// copies are disjoint, and the no-packet offset stays outside the buffer behind tile 1's offsets.
+int wide_gen32_layout_check(int R) {
+    if (R < 1 || R > kRows32) return -1;
+    int bad = wide_gen_layout_check(R < kRowsW ? R : kRowsW);
+    if (R > kRowsW) bad += wide_gen_layout_check(R - kRowsW);
+    const unsigned area = (unsigned)GX_GROUP32 * 4u;
+    const int bufs[3] = {GX_X1, GX_H1, GX_Y1}, szs[3] = {GS_X, GS_X, GS_Y};
+    for (int b = 0; b < 3; ++b)
+        for (unsigned sq = 0; sq < 2; ++sq) {
+            const bool y = b == 2;
+            const int upw = y ? GO : GU, np = y ? 1 : 2;
+            std::vector<int> owner(area / 16, -1);
+            int published = 0, matched = 0;
+            for (int w = 0; w < kPM; ++w)
+                for (int cn = 0; cn < R; ++cn)
+                    for (int cul = 0; cul < upw; cul += 4) {
+                        const int tile = cn >> 4, cnl = cn & 15, u = upw * w + cul;
+                        const unsigned lo = (unsigned)tile * kTile1B;
+                        const unsigned o = lo + g_slot(bufs[b], szs[b], sq) + (y ? g_prod_y(u, cnl) : g_prod_x(u, cnl));
+                        if (o % 16 || o < lo || o + 16 > lo + (unsigned)GX_D * 4u || o + 16 > area) { ++bad; continue; }
+                        if (owner[o / 16] >= 0) ++bad;
+                        owner[o / 16] = u * kRows32 + cn;
+                        ++published;
+                    }
+            for (int tile = 0; tile < 2; ++tile)
+                for (int v = 0; v < 8; ++v)
+                    for (int l = 0; l < 64; ++l) {
+                        const int cn = kRowsW * tile + (l & 15);
+                        if (cn >= R) continue;
+                        for (int p = 0; p < np; ++p) {
+                            const unsigned o = (unsigned)tile * kTile1B + g_slot(bufs[b], szs[b], sq) +
+                                               (y ? g_cons_y(v, l) : g_cons_x(v, l)) + 1024u * (unsigned)p;
+                            if (o % 16 || o + 16 > area) { ++bad; continue; }
+                            const int ow = owner[o / 16];
+                            const int want_u = y ? 16 * v + 4 * (l >> 4) : 32 * v + 8 * (l >> 4) + 4 * p;
+                            if (ow != want_u * kRows32 + cn) ++bad;
+                            ++matched;
+                        }
+                    }
+            if (matched != published) ++bad;
+            if ((unsigned long long)kNoOff + g_slot(bufs[b], szs[b], sq) + kTile1B + 1024ull <= 0x7fffffffull) ++bad;
+        }
+    for (int cn = 0; cn < R; ++cn)
+        for (int c = 0; c < 16; ++c) {
+            const unsigned lo = (unsigned)(cn >> 4) * kTile1B + (unsigned)GX_D * 4u;
+            const unsigned o = lo + g_cand(cn & 15, 2 * c);
+            if (o % 16 || o + 16 > lo + (unsigned)(kRowsW * kPM * 2) * 4u || o + 16 > (unsigned)(cn >> 4) * kTile1B + kTile1B)
+                ++bad;
+        }
+    if ((unsigned)GX_D * 4u + (unsigned)(kRowsW * kPM * 2) * 4u > kTile1B || 2u * kTile1B != area) ++bad;  // copies disjoint
+    if ((size_t)kPG * GX_GROUP32 != persist_wide_gen32_xbuf_floats()) ++bad;
+    if ((unsigned long long)kNoOff + (unsigned)GX_D * 4u + kTile1B <= 0x7fffffffull) ++bad;
+    return bad;
+}
+
+// ... and the MOL / BETA logit pairs of both tiles: each tile's pairs by the check above; tile 1's
+// area lies behind tile 0's whole copy, inside the group's area, in the part the reset zeroes
+int wide_gen32_mol_layout_check(int R, int n_logits) {
+    if (R < 1 || R > kRows32 || (n_logits != 30 && n_logits != 2)) return -1;
+    int bad = wide_gen_mol_layout_check(R < kRowsW ? R : kRowsW, n_logits);
+    if (R > kRowsW) bad += wide_gen_mol_layout_check(R - kRowsW, n_logits);
+    const unsigned pairs = (unsigned)(kRowsW * kPM * 2) * 4u;  // bytes of a tile's pair area
+    for (int cn = 0; cn < R; ++cn)
+        for (int k = 0; k < n_logits; ++k) {
+            const unsigned lo = (unsigned)(cn >> 4) * kTile1B + (unsigned)GX_D * 4u;
+            const unsigned o = lo + g_logit(cn & 15, k);
+            if (o % 8 || o + 8 > lo + pairs || o + 8 > (unsigned)GX_GROUP32 * 4u) ++bad;
+            // (the reset zeroes floats f of a copy with f % GX_GROUP >= GX_D)
+            if ((o / 4u) % (unsigned)GX_GROUP < (unsigned)GX_D) ++bad;
+        }
+    if ((unsigned)GX_D * 4u + pairs > kTile1B) ++bad;  // tile 0's pairs end before tile 1's copy
+    if ((unsigned long long)kNoOff + (unsigned long long)GX_D * 4ull + kTile1B + 8ull <= 0x7fffffffull) ++bad;
     return bad;
 }
 

@@ -149,6 +149,13 @@ struct PlanRates {
     // tools/make_rates.py)
     double wide_gen_mol[2] = {3.025, 0.0094};
     double wide_gen_beta[2] = {4.84, 0.033};
+    // the 32-row ring instances of that kernel (k_persist_wide_gen32; launches of 17 .. 32 rows per
+    // group, wrnn_set_gen_wide_rows(32)), base + row x r: BITS 6.476 / 6.464 / 6.555 us, MOL 4.411 /
+    // 4.422 / 4.677 us, Beta 7.413 / 7.932 / 8.415 us at 17 / 23 / 29 rows per group
+    // (profiles/wide_gen32/gen32_{,mol_,beta_}wide_r*.log, least squares: tools/make_rates.py)
+    double wide_gen32[2] = {6.347, 0.0066};
+    double wide_gen32_mol[2] = {3.992, 0.0222};
+    double wide_gen32_beta[2] = {6.001, 0.0835};
     double slice[2] = {60.0, 0.98};                        // us per extra launch, gain threshold
     // rotation: rates of the rotated instance's two bodies by rows per group (the (q + 1)-row
     // one at its single-launch rate; the q-row one the best split measured, §3.0e)
@@ -232,6 +239,7 @@ struct wrnn_handle {
     bool p1_ring = false;      // this call's k_persist launches form P1 in-kernel
     bool p1_stream = false;    // this call writes the [S][B][4H] P1 stream (other kernels)
     bool gen_ring = false;     // geneing: every launch is wide and forms P1 / the noise in-kernel
+    int gen_wide_rows = kPWideRows;  // wrnn_set_gen_wide_rows: 16, or 32 (the 32-row ring instances)
     double last_p1_bytes = 0, last_noise_bytes = 0;  // the per-step streams of the last call (wrnn_stream_info)
     bool sparse_call = false;  // this call's k_persist launches run the sparse instances
     PlanRates rates;           // per-step rates of the launch planner (load_rates, §3.0h)
@@ -2252,8 +2260,13 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
     CHECK(P.ctl.alloc(PC_WORDS * sizeof(unsigned)));
     const bool rr = W.rr, gen = W.gen;
     bool any_wide = false;
-    for (const auto& L : h->p_plan) any_wide |= L.wide;
-    const size_t xfl = gen  ? std::max(persist_gen_xbuf_floats(), any_wide ? persist_wide_gen_xbuf_floats() : 0)
+    bool any32 = false;  // geneing launches of more than 16 rows per group (two column tiles)
+    for (const auto& L : h->p_plan) {
+        any_wide |= L.wide;
+        any32 |= gen && L.wide && L.nr > kPWideRows;
+    }
+    const size_t xfl = gen  ? std::max(persist_gen_xbuf_floats(), any32      ? persist_wide_gen32_xbuf_floats()
+                                                                  : any_wide ? persist_wide_gen_xbuf_floats() : 0)
                        : rr ? std::max(persist_rr_xbuf_floats(), any_wide ? persist_wide_rr_xbuf_floats() : 0)
                             : std::max(persist_xbuf_floats(), any_wide ? persist_wide_xbuf_floats() : 0);
     CHECK(P.xbuf.alloc(xfl * sizeof(float)));
@@ -2515,7 +2528,8 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             }
         }
         if (L.wide)  // sentinel-initialised vector slots (kernels_persist_wide*.hip polls)
-            HIPC(gen  ? persist_wide_gen_reset_xbuf(P.xbuf.f(), st)
+            HIPC(gen  ? (L.nr > kPWideRows ? persist_wide_gen32_reset_xbuf(P.xbuf.f(), st)
+                                           : persist_wide_gen_reset_xbuf(P.xbuf.f(), st))
                  : rr ? persist_wide_rr_reset_xbuf(P.xbuf.f(), st) : persist_wide_reset_xbuf(P.xbuf.f(), st));
         else
             HIPC(hipMemsetAsync(P.xbuf.p, 0, xfl * sizeof(float), st));  // step tags
@@ -2558,7 +2572,10 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
                     awr.p1a = ws.a4.f();
                     awr.p1taps = W.p1taps + (size_t)h->hop * 8;  // the [hop][4] table
                     awr.p1split = W.p1split;
-                    le = launch_persist_wide_gen_ring(awr, st);
+                    le = L.nr > kPWideRows ? launch_persist_wide_gen32_ring(awr, st)
+                                           : launch_persist_wide_gen_ring(awr, st);
+                } else if (L.nr > kPWideRows) {
+                    return fail(WRNN_ERR_INVALID, "32-row wide launch in a call with P1 / noise streams");
                 } else {
                     le = launch_persist_wide_gen(aw, st);
                 }
@@ -2796,6 +2813,9 @@ static const RateKey kRateKeys[] = {
     {"wide_gen", nullptr, nullptr, nullptr, &PlanRates::wide_gen},
     {"wide_gen_mol", nullptr, nullptr, nullptr, &PlanRates::wide_gen_mol},
     {"wide_gen_beta", nullptr, nullptr, nullptr, &PlanRates::wide_gen_beta},
+    {"wide_gen32", nullptr, nullptr, nullptr, &PlanRates::wide_gen32},
+    {"wide_gen32_mol", nullptr, nullptr, nullptr, &PlanRates::wide_gen32_mol},
+    {"wide_gen32_beta", nullptr, nullptr, nullptr, &PlanRates::wide_gen32_beta},
     {"slice", nullptr, nullptr, nullptr, &PlanRates::slice},
     {"rot9", nullptr, &PlanRates::rot9, nullptr, nullptr},
     {"rot9_sp", nullptr, &PlanRates::rot9_sp, nullptr, nullptr},
@@ -2906,6 +2926,10 @@ struct PlanIn {
     bool has_wide_gen = false;     // geneing BITS image (512 / 1024 classes)
     bool has_wide_gen_mol = false;   // geneing MOL image (30 logits)
     bool has_wide_gen_beta = false;  // geneing Beta image (2 logits)
+    // geneing: the head's 32-row ring instances are selected (wrnn_set_gen_wide_rows / env
+    // WRNN_GEN_WIDE_ROWS) and can run -- spill-free, and the call can take the ring (the per-frame
+    // P1 form exists, WRNN_GEN_RING is not 0): established before a 32-row launch is priced
+    bool gen32 = false;
     int scr[2][kPNR + 1] = {};     // fatchord k_persist [stream | ring][nr]
     int scr_sp[kPNR + 1] = {};     // sparse instances
     int scr_rot[2][kPNR + 1] = {}; // rotated instance of this topology / mode [dense | sparse][nr]
@@ -2927,7 +2951,8 @@ struct PlanOut {
 
 // The persistent launch plan (consecutive launches over row batches; launch k runs rows
 // rb_k + g + 8 r, r < nr_k, in every XCD group g): the cheapest mix of register-resident
-// (nr <= 4, spill-free variants) and wide MFMA launches (nr <= 16) by the per-step rates, then
+// (nr <= 4, spill-free variants) and wide MFMA launches (nr <= 16; geneing with 32 rows selected:
+// nr <= 32 in plans of wide launches only) by the per-step rates, then
 // time-sliced wide launches (§3.0f) or a row rotation (§3.0e) when those are cheaper.
 void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
     out = PlanOut();
@@ -2972,6 +2997,7 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
     }
     if (in.ok) {
         std::vector<Opt> opts;
+        bool gen_wide = false;  // geneing: this call's head is offered wide launches
         if (in.fat) {
             const double* us = in.c10 ? R.fat10 : R.fat9;
             const double* us_sp = in.c10 ? R.fat10_sp : R.fat9_sp;
@@ -3006,6 +3032,7 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
                 (in.wmode == 1 || B > kPG * kPNR) && (in.wide_scr == 0 || in.allow_wide_scratch)) {
                 if (in.wmode == 1) opts.clear();
                 for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, R.wide_gen[0] + R.wide_gen[1] * r});
+                gen_wide = true;
             }
             // geneing MOL / Beta: the same rule, each head by its own image and its own key (the
             // MOL instances run spill-free; the Beta ones may keep the frame k_persist_gen BETA is
@@ -3017,6 +3044,7 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
                 const double* k = gen_mol ? R.wide_gen_mol : R.wide_gen_beta;
                 if (in.wmode == 1) opts.clear();
                 for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, k[0] + k[1] * r});
+                gen_wide = true;
             }
         }
         if (in.nr_max > 0) {  // diagnostic: variant A/B (WRNN_PERSIST_NR_MAX)
@@ -3025,7 +3053,8 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
                        opts.end());
             if (opts.empty()) opts.push_back({c, false, 1.0});
         }
-        if (!opts.empty()) {
+        // the cheapest sequence of launches from `opts` over the call's rows
+        auto solve = [&](const std::vector<Opt>& opts, std::vector<wrnn_handle::PLaunch>& lplan) {
             // best[r]: cheapest plan for r rows; pick[r]: its first launch
             std::vector<double> best(B + 1, 0.0);
             std::vector<int> pick(B + 1, -1);
@@ -3042,11 +3071,31 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
             int rb = 0;
             for (int r = B; r > 0;) {
                 const Opt& o = opts[pick[r]];
-                out.lplan.push_back({rb, o.nr, o.wide});
+                lplan.push_back({rb, o.nr, o.wide});
                 rb += kPG * o.nr;
                 r = std::max(0, r - kPG * o.nr);
             }
-            out.plan_us = best[B];
+            return best[B];
+        };
+        if (!opts.empty()) out.plan_us = solve(opts, out.lplan);
+        // geneing, 32 rows selected: the 32-row ring instances read no stream, so they enter only
+        // plans whose launches are all wide -- the cheapest all-wide plan over 1 .. 32 rows per
+        // group (launches of at most 16 on the existing instances, by their own keys) replaces the
+        // plan above when it is cheaper. The MOL draw stream is padded to the 32-row launch
+        if (in.gen && in.gen32 && gen_wide && in.nr_max <= 0 && !out.lplan.empty() &&
+            (!mol || (double)S * (B + kPG * kPWideGen32Rows) * kMolNoise * 4.0 < 2147483648.0)) {
+            const double* k = in.mode == WRNN_MODE_RAW ? R.wide_gen32
+                            : in.mode == WRNN_MODE_MOL ? R.wide_gen32_mol : R.wide_gen32_beta;
+            std::vector<Opt> wopts;
+            for (const Opt& o : opts)
+                if (o.wide) wopts.push_back(o);
+            for (int r = kPWideRows + 1; r <= kPWideGen32Rows; ++r) wopts.push_back({r, true, k[0] + k[1] * r});
+            std::vector<wrnn_handle::PLaunch> lp32;
+            const double us32 = solve(wopts, lp32);
+            if (us32 < out.plan_us - 1e-9) {
+                out.lplan = std::move(lp32);
+                out.plan_us = us32;
+            }
         }
     }
     // time-sliced wide launches, when cheaper than the plan above by the same rates (P1 formed
@@ -3160,6 +3209,11 @@ StreamPlan plan_streams(const PlanIn& in, const PlanOut& out, bool p1x4, bool ge
         const bool streams_fit = cap_p1 + noise <= kPersistWsBytes;
         const bool can = gen_frames && all_wide && out.wrot.empty() && in.mode >= 0 && in.mode <= 2;
         sp.gen_ring = can && sw != 0 && (sw == 1 || !streams_fit || kGenRingDefault[in.mode]);
+        // (a 32-row launch exists only as a ring instance: plan_call offers it only where `can`
+        // holds and the switch is not 0, so its plan always takes the ring)
+        bool any32 = false;
+        for (const auto& L : out.lplan) any32 |= L.wide && L.nr > kPWideRows;
+        if (any32) sp.gen_ring = can && sw != 0;
         if (sp.gen_ring) {
             sp.p1_stream = false;
             if (raw) noise = 0.0;  // (MOL keeps its k_mol_noise stream)
@@ -3309,10 +3363,7 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
     // PERSIST launch plan (plan_call): register-resident and wide launches by the rates of
     // h->rates, then time-sliced wide launches or a row rotation
     PlanOut pout;
-    const PlanIn pin = plan_inputs(h, B, S);
-    plan_call(pin, h->rates, pout);
-    const auto& lplan = pout.lplan;
-    const int Bplan = pout.Bplan;
+    PlanIn pin = plan_inputs(h, B, S);
     // geneing: the wide launches' ring instances (P1 and the BITS noise formed in-kernel) need the
     // per-frame P1 form, spill-free instances and frame tables inside one 2-GiB buffer range.
     // WRNN_GEN_RING=0|1 (read per call) forces the streams / the ring where it is possible
@@ -3322,6 +3373,18 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
                             h->pw.p1split >= 0 && p1_frames_enabled() &&
                             persist_wide_gen_ring_scratch(h->cfg.mode) == 0 &&
                             (double)(Fr + 1) * 4 * h->H * sizeof(float) < 2147483648.0;
+    // 32-row launches (wrnn_set_gen_wide_rows, env WRNN_GEN_WIDE_ROWS=16|32 read per call): only
+    // where the ring can be taken and the head's 32-row instance runs within its scratch rule
+    int wide_rows = h->gen_wide_rows;
+    if (const char* env = std::getenv("WRNN_GEN_WIDE_ROWS")) {
+        const int v = std::atoi(env);
+        if (v == kPWideRows || v == kPWideGen32Rows) wide_rows = v;
+    }
+    pin.gen32 = wide_rows == kPWideGen32Rows && gen_frames && gen_ring_sw != 0 &&
+                persist_wide_gen32_usable(h->cfg.mode);
+    plan_call(pin, h->rates, pout);
+    const auto& lplan = pout.lplan;
+    const int Bplan = pout.Bplan;
     const StreamPlan splan = plan_streams(pin, pout, h->pw.p1x4, gen_frames, gen_ring_sw);
     bool use_p = false;
     if (want != WRNN_ENGINE_CHAIN) {
@@ -3784,6 +3847,16 @@ int wrnn_stage_timing(wrnn_handle* h, int stage, double* avg_us, int* launches) 
     return WRNN_OK;
 }
 
+int wrnn_set_gen_wide_rows(wrnn_handle* h, int rows) {
+    if (!h) return fail(WRNN_ERR_INVALID, "null handle");
+    if (rows != kPWideRows && rows != kPWideGen32Rows)
+        return fail(WRNN_ERR_INVALID, "rows per group of a wide launch must be 16 or 32");
+    if (rows == kPWideGen32Rows && h->cfg.model_type != WRNN_MODEL_GENEING)
+        return fail(WRNN_ERR_INVALID, "32-row wide launches exist for the geneing topology only");
+    h->gen_wide_rows = rows;
+    return WRNN_OK;
+}
+
 int wrnn_set_engine(wrnn_handle* h, int engine) {
     if (!h) return fail(WRNN_ERR_INVALID, "null handle");
     if (engine != WRNN_ENGINE_AUTO && engine != WRNN_ENGINE_CHAIN && engine != WRNN_ENGINE_PERSIST)
@@ -3891,6 +3964,18 @@ int wrnn_debug_wide_gen_mol_layout(int rows_per_group, int n_logits) {
     return bad;
 }
 
+int wrnn_debug_wide_gen32_layout(int rows_per_group) {
+    const int bad = wide_gen32_layout_check(rows_per_group);
+    if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..32");
+    return bad;
+}
+
+int wrnn_debug_wide_gen32_mol_layout(int rows_per_group, int n_logits) {
+    const int bad = wide_gen32_mol_layout_check(rows_per_group, n_logits);
+    if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..32 and n_logits 30 (MOL) or 2 (Beta)");
+    return bad;
+}
+
 int wrnn_debug_wide_mol_layout(int rows_per_group) {
     const int bad = wide_mol_layout_check(rows_per_group);
     if (bad < 0) return fail(WRNN_ERR_INVALID, "rows_per_group must be 1..16");
@@ -3984,8 +4069,9 @@ static int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_l
     // flags: 1 sparse image, 2 P1 ring / per-frame P1 (fatchord, runtimeracer), 4 wide images
     // (fatchord RAW / MOL, runtimeracer RAW, geneing BITS with 512 or 1024 classes), 16 the
     // runtimeracer MOL wide image, 32 the geneing MOL wide image, 64 the geneing Beta wide image;
-    // every variant spill-free. (128, geneing in-kernel conditioning, does not enter the plan:
-    // wrnn_debug_stream_bytes)
+    // every variant spill-free. (128, geneing in-kernel conditioning, enters the plan only through
+    // 256: the geneing 32-row ring instances are available and selected -- it needs 128 and the
+    // head's flag 4 / 32 / 64; wrnn_debug_stream_bytes)
     in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.force_sp = in.sp && (flags & 8);
     in.p1ring = in.fat && (flags & 2);
@@ -3996,6 +4082,7 @@ static int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_l
     in.has_wide_gen = in.gen && (flags & 4) && mode == WRNN_MODE_RAW && (in.n == 512 || in.n == 1024);
     in.has_wide_gen_mol = in.gen && (flags & 32) && mode == WRNN_MODE_MOL;
     in.has_wide_gen_beta = in.gen && (flags & 64) && mode == WRNN_MODE_BETA;
+    in.gen32 = (flags & 256) && (flags & 128) && (in.has_wide_gen || in.has_wide_gen_mol || in.has_wide_gen_beta);
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
     return WRNN_OK;
 }

@@ -427,6 +427,18 @@ int persist_wide_gen_ring_scratch(int mode);  // ... of its ring instances (a ri
 int wide_gen_layout_check(int rows_per_group);
 // host: violations of the MOL (30) / BETA (2) logit-pair layout; -1 for bad arguments
 int wide_gen_mol_layout_check(int rows_per_group, int n_logits);
+// 32-row ring instances of the wide kernel (k_persist_wide_gen32): up to kPWideGen32Rows rows per
+// XCD group as two MFMA column tiles, ring form only; each tile has its own copy of the group's
+// exchange area, so the xbuf and its reset are twice the 16-row kernel's
+constexpr int kPWideGen32Rows = 32;
+hipError_t launch_persist_wide_gen32_ring(const PersistGenRingArgs& a, hipStream_t s);
+size_t persist_wide_gen32_lds_bytes();
+size_t persist_wide_gen32_xbuf_floats();
+hipError_t persist_wide_gen32_reset_xbuf(float* xbuf, hipStream_t s);
+int persist_wide_gen32_scratch(int mode);  // scratch bytes of the mode's 32-row instances (-1: none)
+bool persist_wide_gen32_usable(int mode);  // spill-free (Beta: at most its 16-byte frame)
+int wide_gen32_layout_check(int rows_per_group);  // 1 .. 32 rows; violations, -1 for bad arguments
+int wide_gen32_mol_layout_check(int rows_per_group, int n_logits);
 int persist_gen_rot_scratch(int nr, int mode);  // the rotated BITS / MOL instance's scratch bytes (-1: none)
 hipError_t launch_persist_gen_init(const PersistGenArgs& a, hipStream_t s);
 int persist_gen_variant_ok(int nr, int cpw, int mode);

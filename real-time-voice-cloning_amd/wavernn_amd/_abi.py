@@ -42,7 +42,8 @@ EXPORTED = [
     'wrnn_set_utt_streams', 'wrnn_set_fold_ranges', 'wrnn_set_debug_steps', 'wrnn_debug_logits', 'wrnn_debug_wide_layout',
     'wrnn_debug_wide_mol_layout', 'wrnn_debug_wide_gen_layout', 'wrnn_debug_wide_rr_mol_layout',
     'wrnn_debug_wide_gen_mol_layout', 'wrnn_sparse_info', 'wrnn_set_rates', 'wrnn_get_rates', 'wrnn_debug_plan',
-    'wrnn_stream_info', 'wrnn_debug_stream_bytes',
+    'wrnn_stream_info', 'wrnn_debug_stream_bytes', 'wrnn_set_gen_wide_rows', 'wrnn_debug_wide_gen32_layout',
+    'wrnn_debug_wide_gen32_mol_layout',
 ]
 
 
@@ -119,6 +120,7 @@ def load_library(path=None):
                                                c_int, c_int, c_void_p, c_void_p, c_size_t,
                                                P(c_int), P(c_int), PROGRESS_FN, c_void_p]),
         'wrnn_set_engine': (c_int, [c_void_p, c_int]),
+        'wrnn_set_gen_wide_rows': (c_int, [c_void_p, c_int]),
         'wrnn_last_engine': (c_int, [c_void_p, P(c_int)]),
         'wrnn_fallback_info': (c_int, [c_void_p, P(c_int), ctypes.c_char_p, c_size_t]),
         'wrnn_enable_stage_timing': (c_int, [c_void_p, c_int]),
@@ -162,6 +164,8 @@ def load_library(path=None):
         'wrnn_debug_wide_gen_layout': (c_int, [c_int]),
         'wrnn_debug_wide_rr_mol_layout': (c_int, [c_int]),
         'wrnn_debug_wide_gen_mol_layout': (c_int, [c_int, c_int]),
+        'wrnn_debug_wide_gen32_layout': (c_int, [c_int]),
+        'wrnn_debug_wide_gen32_mol_layout': (c_int, [c_int, c_int]),
         'wrnn_debug_logits': (c_int, [c_void_p, c_int, c_int, P(ctypes.c_float), c_size_t]),
     }
     # (an A/B build given by WRNN_LIB may predate an entry point: it is left unbound)

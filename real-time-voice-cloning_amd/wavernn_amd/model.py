@@ -210,6 +210,13 @@ class WaveRNN:
             raise ValueError(f'unknown engine {engine!r}; expected one of {sorted(_abi.ENGINES)}')
         _abi.check(self._lib.wrnn_set_engine(self._h, _abi.ENGINES[engine]))
 
+    def set_wide_rows(self, rows):
+        """Row capacity per XCD group of the geneing wide launches for later calls: 16 (default)
+        or 32 (launches of 17 .. 32 rows per group on the 32-row instances, in calls whose launches
+        are all wide; same results bit for bit). ValueError for anything else, or 32 on a model
+        that is not geneing. Env WRNN_GEN_WIDE_ROWS=16|32 overrides it per call."""
+        _abi.check(self._lib.wrnn_set_gen_wide_rows(self._h, int(rows)))
+
     def last_engine(self):
         """Engine ('chain' or 'persist') that ran the last call."""
         e = ctypes.c_int()

@@ -21,6 +21,10 @@ time) and writes `key v1 .. v4` lines for the keys it found; the runtime
   <dir>/gen_mol_wide_r<k>.log, <dir>/gen_beta_wide_r<k>.log (geneing MOL / Beta ('RAW'), every launch
     wide at k rows per group, WRNN_PERSIST_WIDE=1; at least two fills) -> wide_gen_mol,
     wide_gen_beta = base, per row (least squares)
+  <dir>/gen32_wide_r<k>.log, <dir>/gen32_mol_wide_r<k>.log, <dir>/gen32_beta_wide_r<k>.log (geneing BITS /
+    MOL / Beta, one 32-row launch at k = 17 .. 32 rows per group, WRNN_PERSIST_WIDE=1 and
+    WRNN_GEN_WIDE_ROWS=32; at least two fills) -> wide_gen32, wide_gen32_mol, wide_gen32_beta = base,
+    per row (least squares)
 Later directories override earlier ones. The rotation tables keep the runtime's defaults unless
 a key is already in the file given as OUT (kept lines are carried over).
 """
@@ -88,6 +92,16 @@ def main():
             src['wide_rr_mol'] = d
         for pre, key in (('gen_mol_wide_r', 'wide_gen_mol'), ('gen_beta_wide_r', 'wide_gen_beta')):
             pts = [(k, us_step(line_of(os.path.join(d, f'{pre}{k}.log')))) for k in range(1, 17)]
+            pts = [(k, v) for k, v in pts if v is not None]
+            if len(pts) >= 2:
+                mk, mv = sum(k for k, _ in pts) / len(pts), sum(v for _, v in pts) / len(pts)
+                per_row = sum((k - mk) * (v - mv) for k, v in pts) / sum((k - mk) ** 2 for k, _ in pts)
+                per_row = max(per_row, 0.001)
+                keys[key] = [round(mv - per_row * mk, 3), round(per_row, 4)]
+                src[key] = d
+        for pre, key in (('gen32_wide_r', 'wide_gen32'), ('gen32_mol_wide_r', 'wide_gen32_mol'),
+                         ('gen32_beta_wide_r', 'wide_gen32_beta')):
+            pts = [(k, us_step(line_of(os.path.join(d, f'{pre}{k}.log')))) for k in range(17, 33)]
             pts = [(k, v) for k, v in pts if v is not None]
             if len(pts) >= 2:
                 mk, mv = sum(k for k, _ in pts) / len(pts), sum(v for _, v in pts) / len(pts)
