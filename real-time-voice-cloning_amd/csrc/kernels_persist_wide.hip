@@ -28,15 +28,12 @@
 // Every spin is bounded; on a timeout / error the kernel sets PC_ERR and every wave exits at
 // its next barrier.
 #include "wrnn_kernels.h"
-#include "persist_common.h"
+#include "persist_wide_common.h"
 #include "philox.h"
-#include "wide_layout.h"
 
 #include <vector>
 
 namespace wrnn {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 // ---- exchange area per group (floats) ---------------------------------------------------
 // One published vector (x1, h1, x2, h2, y1, y2) per step: two slots (step parity), each
@@ -51,7 +48,6 @@ using wide::WSLOT;
 using wide::WV;
 using wide::WX_D;
 using wide::WX_GROUP;
-constexpr unsigned kSent = 0x7fbadbadu;  // a signalling NaN: no arithmetic result is ever this
 enum WBuf : int { WB_X1 = 0, WB_H1, WB_X2, WB_H2, WB_Y1, WB_Y2, WB_N };
 static_assert(WB_N == wide::kBufs, "one slot pair per published vector");
 // ---- LDS (floats) -------------------------------------------------------------------------
@@ -78,34 +74,12 @@ static_assert(sizeof(RowInfo) == 24, "RowInfo is 6 words");
 // register tiles of a wave: 0-2 W_ih2x r,z,n | 3-5 W_hh1 r,z,n | 6 fc1 | 7 fc2 | 8 fc3
 constexpr int kWTiles = 9;
 
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float f4c(const float4& q, int i) {
-    return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w;
-}
 // B operand of k-step ks from the 4 packets of a hop (packet p holds k-steps 4p .. 4p + 3)
 __device__ __forceinline__ float bop(const u4v (&cc)[4], int ks) {
     const u4v& q = cc[ks >> 2];
     return __uint_as_float((ks & 3) == 0 ? q.x : (ks & 3) == 1 ? q.y : (ks & 3) == 2 ? q.z : q.w);
 }
-// Partial tiles: element (row n, column o) of a [16][16] tile sits at n * 16 + wsw(n, o), the
-// 16-byte column slots XOR-swizzled by row: an MFMA lane's 16-byte store (row bn, columns
-// 4c .. 4c + 3) and the epilogue's row reads are then both conflict-free (a ds_write_b128 is
-// served 8 contiguous lanes at a time on 32 banks: unswizzled, rows 64 B apart put 8 rows on 2
-// slots -- 4-way, 24 extra LDS cycles per store, ~2300 per CU and step; SQ_LDS_BANK_CONFLICT,
-// profiles/r03/pmc/c4_sq)
-__device__ __forceinline__ int wsw(int n, int o) { return ((((o >> 2) ^ (n >> 1)) & 3) << 2) | (o & 3); }
-
-__device__ __forceinline__ bool p_ready(const u4v& q) {
-    // bitwise: the short-circuit form compiled to a branch and a wait per packet
-    return (q.x != kSent) & (q.y != kSent) & (q.z != kSent) & (q.w != kSent);
-}
-
-// LDS-only workgroup barrier: no wait on outstanding global loads (prefetches stay in flight)
-__device__ __forceinline__ void wbar() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+// (mfma4, f4c, the partial tiles' swizzle wsw, packet_ready and lds_barrier: persist_wide_common.h)
 
 // Poll this lane's 4 packets of one hop buffer slot (byte offset of packet 0: voff; packet p at
 // voff + 1 KiB p; so: the buffer and slot) until no value is the sentinel, all 4 in flight on
@@ -135,9 +109,8 @@ __device__ __forceinline__ void w_issue1(rsrc_t xr, unsigned voff, unsigned so, 
     asm volatile("" : "+v"(vo));
     c = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024u * i, so, kCpNT);
 }
-// On a timeout the first poller records its site in PC_WHERE (`where`: site << 28 | slot << 22;
-// the wave is added here), whether its packets were missing (PC_WHERE + 1) and the step
-// (PC_WHERE + 2, all 32 bits), for the error message.
+// On a timeout the first poller records its site, whether its packets were missing and the step
+// (spin_give_up).
 __device__ __forceinline__ bool w_poll(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v (&cc)[4],
                                        unsigned* ctl, unsigned where, unsigned step, bool pre = false) {
     const unsigned t0 = p_now();
@@ -146,7 +119,7 @@ __device__ __forceinline__ bool w_poll(rsrc_t xr, unsigned voff, unsigned so, bo
     {
         bool ok = true;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ok &= p_ready(cc[i]);
+        for (int i = 0; i < 4; ++i) ok &= packet_ready(cc[i]);
         if (__all(ok)) return true;
     }
     while (true) {
@@ -158,24 +131,14 @@ __device__ __forceinline__ bool w_poll(rsrc_t xr, unsigned voff, unsigned so, bo
         {
             bool ok = true;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) ok &= p_ready(cc[i]);
+            for (int i = 0; i < 4; ++i) ok &= packet_ready(cc[i]);
             if (__all(ok)) return true;
         }
         if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
-            if (!ld_sc1_u(ctl + PC_ERR)) {  // the first to time out records where
-                bool mok = true;
+            bool mok = true;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) mok &= p_ready(cc[i]);
-                const bool mbad = !__all(mok);
-                // (the wave index read back as a scalar: a per-lane form was precomputed per site
-                // before the step loop and held VGPRs)
-                const unsigned wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-                if ((threadIdx.x & 63) == 0 && atomicCAS(ctl + PC_WHERE, 0u, where | (wv << 19)) == 0u) {
-                    ctl[PC_WHERE + 1] = mbad ? 1u : 0u;
-                    ctl[PC_WHERE + 2] = step;
-                }
-            }
-            if ((threadIdx.x & 63) == 0) atomicMax(ctl + PC_ERR, 2u);
+            for (int i = 0; i < 4; ++i) mok &= packet_ready(cc[i]);
+            spin_give_up(ctl, where, step, !__all(mok));
             return false;
         }
     }
@@ -506,13 +469,13 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
             // hop D (gh2, after the candidate store). Waves 4-7 poll x1 of OTHER slots only
             // (wave v: slots 4v .. 4v + 3), so nothing orders those reads before this store but
             // a barrier: every wave reaches it after its hop-E poll anyway.
-            wbar();
+            lds_barrier();
 #pragma unroll
             for (int j = 0; j < 3; ++j)
                 *reinterpret_cast<v4f*>(lds + WL_PA + ((v * 3 + j) * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc[j];
         }
         if (fail) lds[WL_FAIL] = 1.f;
-        wbar();
+        lds_barrier();
         WSTAMP(2);
         // The step's one failure check: a wave whose poll gave up (timeout, or PC_ERR raised by
         // another slot) finishes the step on whatever its registers hold; every other poll of
@@ -573,7 +536,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
             *reinterpret_cast<v4f*>(lds + WL_PS + (v * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc0 + acc1;
         }
         if (fail) lds[WL_FAIL] = 1.f;
-        wbar();
+        lds_barrier();
         WSTAMP(5);
         // fc1 epilogue (waves 0-3): y1 = relu(fc1 x2 + fc1[:, 512:] a3 + b) -> publish
         if (lo) {
@@ -626,7 +589,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
             *reinterpret_cast<v4f*>(lds + WL_PS + (v * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc0 + acc1;
         }
         if (fail) lds[WL_FAIL] = 1.f;
-        wbar();
+        lds_barrier();
         WSTAMP(7);
         if (lo) {  // fc2 epilogue: y2 = relu(fc2 y1 + fc2[:, 512:] a4 + b) -> publish
             float y = 0.f;
@@ -689,12 +652,12 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
                 acc0 = mfma4(f4c(fb[ks >> 2], ks & 3), bop(cc, ks), acc0);
                 acc1 = mfma4(f4c(fb[ks >> 2], (ks + 1) & 3), bop(cc, ks + 1), acc1);
             }
-            wbar();  // (every wave's gh1 / gh2 reads of PH are done)
+            lds_barrier();  // (every wave's gh1 / gh2 reads of PH are done)
             *reinterpret_cast<v4f*>(lds + WL_PH + (v * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc0 + acc1;
             prefetch_d();  // (after the products: fewer registers live over them)
         }
         if (fail) lds[WL_FAIL] = 1.f;
-        wbar();
+        lds_barrier();
         WSTAMP(9);
         if (lo) {
             // fc3 epilogue: the candidate key (cand_key.h: l_k + G_k formed exactly as an fp32 pair)
@@ -768,8 +731,11 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
                 // lane (row cn, cul) polls logits cul and 16 + cul of its row (tag: the whole seq);
                 // a lane without a logit loads from an out-of-range offset (reads 0, not waited for)
                 const bool ra = cell && cul < a.n_classes, rb = cell && 16 + cul < a.n_classes;
-                unsigned va = ra ? wide::logit_off(cn, cul) : wide::kNoOffset;
-                unsigned vb = rb ? wide::logit_off(cn, 16 + cul) : wide::kNoOffset;
+                // (poll_logit_pairs written out with its own timeout report: the kernel sits at the
+                // 256-VGPR limit, and with spin_give_up here the ROT MOL DBG instance's register
+                // allocation changes -- its scratch, tools/isa_check.py resources_of)
+                unsigned va = ra ? wide::logit_off(cn, cul) : kNoOff;
+                unsigned vb = rb ? wide::logit_off(cn, 16 + cul) : kNoOff;
                 asm volatile("" : "+v"(va), "+v"(vb));
                 u2v qa, qb;
                 const unsigned t0s = p_now();
@@ -789,28 +755,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
                 }
                 // the sample: k_persist<MOL>'s operations in its order (kernels_persist.hip, "MOL:")
                 const float la = __uint_as_float(qa.x), lb = __uint_as_float(qb.x);
-                float bv;
-                {
-#pragma clang fp contract(off)
-                    bv = cul < 10 ? la - pg : -INFINITY;
-                }
-                int bi = cul < 10 ? cul : 0x7fffffff;
-                row16_argmax(bv, bi);  // first max over k < 10; every lane of the row gets it
-                bi = bi < 10 ? bi : 0;
-                const int base = l & 48;  // lane 0 of this lane's row
-                // l[10 + bi]: the first value of lane 10 + bi, or the second of lane bi - 6
-                const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
-                const float mean = bi < 6 ? m0 : m1;
-                float ls = __shfl(lb, base + 4 + bi);  // l[20 + bi]: the second value of lane 4 + bi
-                const float lu = __shfl(pg, base + 10);
-                {
-#pragma clang fp contract(off)
-                    const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
-                    ls = ls < lsmin ? lsmin : ls;
-                    x = mean + expf(ls) * lu;
-                    x = x < -1.f ? -1.f : x;
-                    x = x > 1.f ? 1.f : x;
-                }
+                x = mol_sample_row16(la, lb, pg, cul, l);
                 pg = pgn;
                 if (w == 0 && cell && cul == 0) {
                     int nn = cn;
@@ -819,34 +764,14 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide(PersistArgs a) {
                     bst(x, mk_rsrc(a.samples), (unsigned)(vm.x * a.ld + vm.y) * 4u, (unsigned)t * 4u);
                 }
             } else {
-                const unsigned want = key_tag(seq);
-                u4v q = {0u, want, 0u, want};
-                const unsigned t0s = p_now();
-                unsigned nsp = 0;
-                while (true) {
-                    if (cell) {
-                        unsigned vo = wide::cand_off(cn, 2 * cul);
-                        asm volatile("" : "+v"(vo));
-                        q = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, WX_D * 4, kCpNT);
-                    }
-                    if (__all((q.y & kKeyTagMask) == want && (q.w & kKeyTagMask) == want)) break;
-                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
-                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
-                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(9) | ((unsigned)v << 19)) == 0u)
-                            a.ctl[PC_WHERE + 2] = (unsigned)t;
-                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
-                        fail = true;
-                        break;
-                    }
-                }
+                u4v q;
+                fail |= !poll_cand_couple(xr, cell, wide::cand_off(cn, 2 * cul), WX_D * 4, key_tag(seq), a.ctl, wh(9),
+                                          (unsigned)t, false, q);
                 uint32_t bh = q.x, bl = q.y;
                 kmax_take(bh, bl, q.z, q.w);
                 row16_kmax(bh, bl);
                 const int bi = key_cls(bl);
-                {
-#pragma clang fp contract(off)
-                    x = (2.0f * (float)bi) / (float)(a.n_classes - 1) - 1.0f;
-                }
+                x = bits_sample_of(bi, a.n_classes);
                 if (w == 0 && cell && cul == 0) {
                     int nn = cn;
                     asm volatile("" : "+v"(nn));

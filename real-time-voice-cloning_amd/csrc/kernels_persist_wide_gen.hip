@@ -56,14 +56,21 @@
 // there are no labels. The area is single-buffered like the candidates: a slot publishes the
 // logits of step t + 1 only after y1 of t + 1 of every slot, which follows x1 of t + 1 of every
 // slot, which every slot publishes after its hop 3 of step t.
-//   MOL:  k_persist_gen's operations in its order (first max over the 10 mixture logits minus
-//         their draws, mean, log-scale clamp, mean + exp(ls) lu, clamp to [-1, 1]); the 11 draws of
+//   MOL:  k_persist_gen's operations in its order (persist_wide_common.h mol_sample_row16: first
+//         max over the 10 mixture logits minus their draws, mean, log-scale clamp,
+//         mean + exp(ls) lu, clamp to [-1, 1]); the 11 draws of
 //         a row come from the k_mol_noise stream [S][B][kMolNoise], lane cul holds draw cul,
 //         loaded one step ahead.
 //   Beta: lanes 0 and 1 of a row draw X ~ Gamma(exp l0), Y ~ Gamma(exp l1) concurrently (philox.h
 //         gamma_mt, keyed by the row's step, fold and stream), lane 0 forms 2 X / (X + Y) - 1.
+//
+// One step body for both kernels: k_persist_wide_gen (16 rows) and k_persist_wide_gen32 (32 rows)
+// call the same step pieces (gen_* below, on a GenCell and the LDS layout GenLds<tiles>); a kernel
+// keeps only what differs, its MFMA loops over one or two column tiles and its ring work. The
+// helpers shared with the other wide kernels (sentinel, polls, samplers, timeout report) are in
+// persist_wide_common.h.
 #include "wrnn_kernels.h"
-#include "persist_common.h"
+#include "persist_wide_common.h"
 #include "philox.h"
 
 #include <type_traits>
@@ -72,14 +79,11 @@
 namespace wrnn {
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int GH = kRH;        // rnn_dims 256
 constexpr int GF = kGF;        // fc_dims 128
 constexpr int GU = GH / kPM;   // GRU units per slot (8)
 constexpr int GO = GF / kPM;   // fc1 outputs per slot (4)
-constexpr int kRowsW = 16;     // rows per group (MFMA N)
-constexpr unsigned kSentG = 0x7fbadbadu;  // a signalling NaN: no arithmetic result is ever this
-constexpr unsigned kNoOff = 0x80000000u;  // lanes without a packet: outside every buffer
+constexpr int kRowsW = 16;     // rows per group and column tile (MFMA N)
 
 // ---- exchange area per group (floats) ---------------------------------------------------
 // x1, h1 (256 units): per step parity slot [e 8][p 2][lane 64] packets of 4 floats; packet p of
@@ -91,6 +95,11 @@ constexpr int GX_X1 = 0, GX_H1 = GX_X1 + 2 * GS_X, GX_Y1 = GX_H1 + 2 * GS_X;
 constexpr int GX_D = GX_Y1 + 2 * GS_Y;  // candidates [row 16][slot 32] (key hi, key lo | tag)
 constexpr int GX_GROUP = GX_D + kRowsW * kPM * 2 + 64;
 static_assert(GX_GROUP % 4 == 0 && GX_D % 4 == 0, "reset works in 16-byte units");
+// 32-row instances: tile 1 (rows 16-31) has its own copy of the whole area behind tile 0's
+constexpr int kRows32 = 2 * kRowsW;
+constexpr unsigned kTile1B = (unsigned)GX_GROUP * 4u;  // byte offset of tile 1's copy in a group's area
+constexpr int GX_GROUP32 = 2 * GX_GROUP;
+static_assert(kTile1B % 16 == 0, "tile 1's copy: 16-byte aligned");
 
 __host__ __device__ constexpr unsigned g_cons_x(int v, int l) { return (unsigned)((v * 2 * 64 + l) * 16); }
 __host__ __device__ constexpr unsigned g_cons_y(int v, int l) { return (unsigned)((v * 64 + l) * 16); }
@@ -114,40 +123,370 @@ __host__ __device__ constexpr unsigned g_logit(int n, int k) { return (unsigned)
 static_assert(kGenLogitsMax == kPM && g_logit(kRowsW - 1, kGenLogitsMax - 1) + 8 == (unsigned)(kRowsW * kPM * 2) * 4u,
               "the logit pairs fill the candidate area");
 
-// ---- LDS (floats) -------------------------------------------------------------------------
-constexpr int WL_RI = 0;         // RowInfo of the group's rows (6 words each)
-constexpr int WL_FAIL = 112;
-constexpr int WL_REG = 116;      // group, slot, registration result (ints)
-constexpr int WL_CB = 128;       // b_hh1 of the slot's units [3][8], then b_f3 of its classes @32
-constexpr int WL_P = 256;        // partial tiles [8 v][nt][16 n][16 m], one buffer per product
-constexpr int WT = 8 * 256;
-constexpr int WP_F1 = WL_P, WP_HH = WP_F1 + WT, WP_F3 = WP_HH + 2 * WT, WL_TOTAL = WP_F3 + 2 * WT;
-// ring instances: P1 of the next step as float4 [16 n][8 units], the step's Gumbel words
-// [16 n][32 (cpw 16: the first 16)] -- one slot each, behind the partial tiles
-constexpr int kGrW = 32;
-constexpr int WL_P1R = WL_TOTAL, WL_GR = WL_P1R + kRowsW * GU * 4, WL_TOTAL_RING = WL_GR + kRowsW * kGrW;
-static_assert(WL_P1R % 4 == 0 && WL_TOTAL_RING * sizeof(float) <= 64 * 1024, "ring arrays: float4-aligned, inside LDS");
-static_assert(sizeof(RowInfo) == 24 && kRowsW * 6 <= WL_FAIL, "RowInfo array overflows");
-static_assert(WL_CB + 32 + 32 <= WL_P, "slot constants overflow");
+// ---- LDS (floats), for NT column tiles of 16 rows (1: the 16-row kernel, 2: the 32-row one) ----
+constexpr int WT = 8 * 256;  // the 8 waves' partials of one 16 x 16 tile
+constexpr int kGrW = 32;     // Gumbel words per row in the ring's noise array
+template <int NT>
+struct GenLds {
+    static constexpr int kRows = NT * kRowsW;
+    static constexpr int RI = 0;                             // RowInfo of the group's rows (6 words each)
+    static constexpr int FAIL = NT == 1 ? 112 : 6 * kRows;   // behind the RowInfo array
+    static constexpr int REG = FAIL + 4;                     // group, slot, registration result (ints)
+    static constexpr int CB = REG + 12;  // b_hh1 of the slot's units [3][8], then b_f3 of its classes @32
+    // partial tiles [tile][8 v][nt][16 n][16 m], one buffer per product (fc1: nt 1, W_hh1 and fc3: 2)
+    static constexpr int P = 256 * NT;
+    static constexpr int F1 = P, HH = F1 + NT * WT, F3 = HH + 2 * NT * WT, TOTAL = F3 + 2 * NT * WT;
+    // ring instances: P1 of the next step as float4 [n][8 units], the step's Gumbel words
+    // [n][32 (cpw 16: the first 16)] -- one slot each, behind the partial tiles
+    static constexpr int P1R = TOTAL, GR = P1R + kRows * GU * 4, TOTAL_RING = GR + kRows * kGrW;
+    static_assert(sizeof(RowInfo) == 24 && kRows * 6 <= FAIL, "RowInfo array overflows");
+    static_assert(CB + 32 + 32 <= P && REG % 4 == 0, "slot constants overflow");
+    static_assert(P % 4 == 0 && P1R % 4 == 0 && WT % 4 == 0, "partial tiles and P1 array: float4-aligned");
+    static_assert(TOTAL_RING * sizeof(float) <= (NT == 1 ? 64 : 160) * 1024, "LDS arrays exceed the kernel's carve");
+};
+// the 32-row layout is the 16-row one with every per-tile and per-row array doubled, in the same order
+static_assert(GenLds<2>::P == 2 * GenLds<1>::P && GenLds<2>::HH - GenLds<2>::F1 == 2 * (GenLds<1>::HH - GenLds<1>::F1) &&
+                  GenLds<2>::F3 - GenLds<2>::HH == 2 * (GenLds<1>::F3 - GenLds<1>::HH) &&
+                  GenLds<2>::TOTAL - GenLds<2>::P == 2 * (GenLds<1>::TOTAL - GenLds<1>::P) &&
+                  GenLds<2>::TOTAL_RING - GenLds<2>::P == 2 * (GenLds<1>::TOTAL_RING - GenLds<1>::P),
+              "GenLds<2> doubles GenLds<1>'s arrays");
 
 constexpr int kWgq = 8;  // float4 weight registers per lane: T0-T2 two each, T3, T4 one each
 
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+// ---- a thread's place in the step -----------------------------------------------------------
+// Workgroup (group g, slot w), wave v (K-eighth v of every product), lane l, MFMA column bn, and
+// the epilogue cell: row cn of the group = column cnl of tile tt, tile row cul. 16-row kernel: the
+// cells lie on waves 0-3, tt = 0; 32-row kernel: tile 1's cells on waves 4-7. xt: byte offset of
+// the cell's tile copy in the group's exchange area (0 for tile 0).
+template <int NT>
+struct GenCell {
+    using L = GenLds<NT>;
+    float* lds;
+    rsrc_t xr;
+    int g, w, v, l, bn, R, g0;
+    int tt, cn, cnl, cul, cu, crow;
+    unsigned xt;
+    bool cell, gcell, fcell;
+    int ntc;              // fc3 tiles of the slot (1 or 2; MOL / BETA: 1)
+    unsigned o_px, o_py;  // publishing lanes: x1 / h1 the first lane of each unit quad, y1 the row's lane 0
+
+    __device__ __forceinline__ unsigned wh(unsigned site) const { return site << 28 | (unsigned)w << 22; }
+    __device__ __forceinline__ const RowInfo& row(int n) const {
+        return reinterpret_cast<const RowInfo*>(lds + L::RI)[n];
+    }
+    // publish the lane's value of step seq as one packet of its quad: slot seq & 1, the
+    // sentinel into slot (seq + 1) & 1. Every lane of the wave issues both stores (a lane that
+    // does not publish uses kNoOff, which the buffer range check drops): no branch around them,
+    // so the compiler's waits after them stay counted (DESIGN §3.0b)
+    __device__ __forceinline__ void pub(int buf, int sz, unsigned off, float val, unsigned seq) const {
+        const float u1 = pdpp<0x39>(val), u2 = pdpp<0x4E>(val), u3 = pdpp<0x93>(val);
+        unsigned vo = off;
+        asm volatile("" : "+v"(vo));
+        __builtin_amdgcn_raw_buffer_store_b128(
+            (u4v){__float_as_uint(val), __float_as_uint(u1), __float_as_uint(u2), __float_as_uint(u3)}, xr, vo,
+            g_slot(buf, sz, seq) + xt, 0);
+        __builtin_amdgcn_raw_buffer_store_b128((u4v){kSent, kSent, kSent, kSent}, xr, vo,
+                                               g_slot(buf, sz, seq + 1u) + xt, 0);
+    }
+    // partial tile j (of nt) of a product, column tile `tile`, into P ([tile][v][nt][n][m], swizzled)
+    __device__ __forceinline__ void put(int P, int nt, int tile, int j, const v4f& acc) const {
+        *reinterpret_cast<v4f*>(lds + P + tile * nt * WT + ((v * nt + j) * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc;
+    }
+    // the cell's sum of the 8 waves' partials of tile j, tile row m (fixed order v = 0 .. 7)
+    __device__ __forceinline__ float psum(int P, int nt, int j, int m) const {
+        float p[8];
+#pragma unroll
+        for (int vv = 0; vv < 8; ++vv) p[vv] = lds[P + tt * nt * WT + ((vv * nt + j) * 16 + cnl) * 16 + wsw(cnl, m)];
+        float acc = 0.f;
+#pragma unroll
+        for (int vv = 0; vv < 8; ++vv) acc += p[vv];
+        return acc;
+    }
+};
+
+// registration of the workgroup; false: the launch is not to run (p_register)
+template <class L>
+__device__ __forceinline__ bool gen_register(unsigned* ctl, float* lds, int& g, int& w) {
+    int* sreg = reinterpret_cast<int*>(lds + L::REG);
+    if (threadIdx.x == 0) {
+        int gg, ss;
+        sreg[2] = p_register(ctl, gg, ss);
+        sreg[0] = gg;
+        sreg[1] = ss;
+    }
+    __syncthreads();
+    if (!sreg[2]) return false;
+    g = __builtin_amdgcn_readfirstlane(sreg[0]);
+    w = __builtin_amdgcn_readfirstlane(sreg[1]);
+    return true;
 }
-__device__ __forceinline__ float f4c(const float4& q, int i) {
-    return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w;
+
+template <int MODE, int NT>
+__device__ __forceinline__ GenCell<NT> gen_cell(const PersistGenArgs& a, float* lds, int g, int w) {
+    GenCell<NT> c;
+    const int tid = threadIdx.x;
+    c.lds = lds;
+    c.g = g;
+    c.w = w;
+    c.v = __builtin_amdgcn_readfirstlane(tid >> 6);
+    c.l = tid & 63;
+    c.bn = c.l & 15;
+    c.R = a.nr;
+    c.g0 = a.rb + g;
+    c.tt = NT == 1 ? 0 : c.v >> 2;
+    c.cn = tid >> 4;
+    c.cnl = NT == 1 ? c.cn : c.cn & 15;
+    c.cul = tid & 15;
+    c.cell = NT == 1 ? tid < 16 * c.R : c.cn < c.R;
+    c.gcell = c.cell && c.cul < GU;  // GRU cell: unit 8 w + cul
+    c.fcell = c.cell && c.cul < GO;  // fc1 cell: output 4 w + cul
+    c.cu = GU * w + (c.cul & 7);
+    c.crow = c.g0 + kPG * (c.cell ? c.cn : 0);
+    c.ntc = MODE == 0 ? a.cpw / 16 : 1;
+    c.xr = mk_rsrc(a.xbuf + (size_t)g * (NT * GX_GROUP));
+    c.xt = (unsigned)c.tt * kTile1B;  // (uniform)
+    c.o_px = c.gcell && (c.cul & 3) == 0 ? g_prod_x(GU * w + c.cul, c.cnl) : kNoOff;
+    c.o_py = c.cell && c.cul == 0 ? g_prod_y(GO * w, c.cnl) : kNoOff;
+    return c;
 }
-__device__ __forceinline__ float u4c(const u4v& q, int i) {
-    return __uint_as_float(i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w);
+
+// ---- weights: K = 256 tile T (< 3), k-step ks at wq[2 T + ks / 4] component ks % 4;
+//      fc3 tile j, k-step ks at wq[6 + j] component ks -------------------------------------
+template <int NT>
+__device__ __forceinline__ void gen_load_weights(const PersistGenArgs& a, const GenCell<NT>& c, float4 (&wq)[kWgq]) {
+    const float4* src = a.wwide + ((size_t)(c.w * 8 + c.v) * kWgq) * 64 + c.l;
+#pragma unroll
+    for (int q = 0; q < kWgq; ++q) wq[q] = src[(size_t)q * 64];
 }
-// conflict-free partial tiles: XOR swizzle of the 16-byte column slots by row (as
-// kernels_persist_wide_rr.hip wsw)
-__device__ __forceinline__ int wsw(int n, int o) { return ((((o >> 2) ^ (n >> 1)) & 3) << 2) | (o & 3); }
-__device__ __forceinline__ bool g_ready(const u4v& q) {
-    return (q.x != kSentG) & (q.y != kSentG) & (q.z != kSentG) & (q.w != kSentG);
+// the group's RowInfo and the slot's biases into LDS, the failure flag cleared
+template <int NT>
+__device__ __forceinline__ void gen_setup_lds(const PersistGenArgs& a, const GenCell<NT>& c) {
+    using L = GenLds<NT>;
+    const int tid = threadIdx.x;
+    float* lds = c.lds;
+    if (tid < c.R) reinterpret_cast<RowInfo*>(lds + L::RI)[tid] = a.rows[c.g0 + kPG * tid];
+    if (tid == 0) lds[L::FAIL] = 0.f;
+    if (tid < 24) lds[L::CB + tid] = a.b_hh1[(tid >> 3) * GH + GU * c.w + (tid & 7)];
+    if (tid >= 32 && tid < 32 + a.cpw) {
+        const int cl = a.cpw * c.w + tid - 32;
+        lds[L::CB + tid] = cl < a.n_classes ? a.b_f3[cl] : 0.f;
+    }
 }
-__device__ __forceinline__ void gbar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// what a cell carries over the launch: its GRU unit's state and input weights, and (MOL / BETA)
+// its places in the draw stream and the logit-pair area
+struct GenState {
+    float h1r, x1c;
+    float vr, vz, vn, w0c;
+    // MOL: lane cul < kMolNoise of a row holds draw cul of its row from the k_mol_noise stream
+    // ([S][B][kMolNoise]); pg is the draw of step t, pgn the one of step t + 1 (clamped at the
+    // last step, where it goes unused)
+    float pg, pgn;
+    unsigned o_mol;
+    // MOL / BETA: the lane's pair in the logit area as producer (slots 0 and 1: logit 16 w + cul)
+    // and as consumer (logits cul and 16 + cul of row cn); kNoOff where there is none
+    bool l_ra, l_rb;
+    unsigned o_lp;
+};
+template <int NT>
+__device__ __forceinline__ GenState gen_state(const PersistGenArgs& a, const GenCell<NT>& c) {
+    GenState s;
+    s.h1r = 0.f;
+    s.x1c = 0.f;
+    if (c.gcell) {  // x1, h1 of step 0 (k_persist_gen_init)
+        const float* st = a.st + (size_t)c.crow * 2 * GH;
+        s.x1c = st[c.cu];
+        s.h1r = st[GH + c.cu];
+    }
+    s.vr = c.gcell ? a.v[c.cu] : 0.f;
+    s.vz = c.gcell ? a.v[GH + c.cu] : 0.f;
+    s.vn = c.gcell ? a.v[2 * GH + c.cu] : 0.f;
+    s.w0c = c.gcell ? a.w0[c.cu] : 0.f;
+    s.pg = 0.f;
+    s.pgn = 0.f;
+    s.o_mol = (unsigned)(c.crow * kMolNoise + c.cul) * 4u;
+    s.l_ra = c.cell && c.cul < a.n_classes;
+    s.l_rb = c.cell && 16 + c.cul < a.n_classes;
+    s.o_lp = c.cell && c.w < 2 && 16 * c.w + c.cul < a.n_classes ? g_logit(c.cnl, 16 * c.w + c.cul) : kNoOff;
+    return s;
+}
+// MOL: the row's draws of step te into pgn
+template <int NT>
+__device__ __forceinline__ void gen_mol_draw(const PersistGenArgs& a, const GenCell<NT>& c, GenState& s, int te) {
+    const int tc = te < a.S ? te : a.S - 1;
+    if (c.cell && c.cul < kMolNoise) s.pgn = bld(mk_rsrc(a.gumbel + (size_t)tc * a.B * kMolNoise), s.o_mol, 0);
+}
+// initial x1, h1 (canonicalised: a signalling NaN in a carried state must not read as the
+// sentinel), as step t0's vectors
+template <int NT>
+__device__ __forceinline__ void gen_pub_initial(const PersistGenArgs& a, const GenCell<NT>& c, const GenState& s) {
+    c.pub(GX_X1, GS_X, c.o_px, __builtin_canonicalizef(s.x1c), (unsigned)a.t0 + 1u);
+    c.pub(GX_H1, GS_X, c.o_px, __builtin_canonicalizef(s.h1r), (unsigned)a.t0 + 1u);
+}
+// fc1 conditioning of frame(t) for the cell's output
+template <int NT>
+__device__ __forceinline__ float gen_fc1_cond(const PersistGenArgs& a, const GenCell<NT>& c, rsrc_t fcr, int t) {
+    float pc = 0.f;
+    if (c.fcell)
+        pc = bld(fcr, (unsigned)(p_frame(c.row(c.cn), t, a.hop) * a.cond_width + a.oF1 + GO * c.w + c.cul) * 4u, 0);
+    return pc;
+}
+// y1 = relu(fc1 partials + conditioning) of the cell's output, published (hop 1's end)
+template <int NT>
+__device__ __forceinline__ void gen_pub_y1(const GenCell<NT>& c, float pc, unsigned seq) {
+    float y = 0.f;
+    if (c.fcell) {
+        y = p_add(c.psum(GenLds<NT>::F1, 1, 0, c.cul), pc);
+        y = y > 0.f ? y : 0.f;
+    }
+    c.pub(GX_Y1, GS_Y, c.o_py, y, seq);
+}
+// ring instances: the cell's noise of step t and P1(t + 1) from the one-slot LDS arrays: written
+// before the step's first barrier (the step before, or the prologue), overwritten only after its
+// second
+template <int MODE, int NT>
+__device__ __forceinline__ void gen_ring_read(const GenCell<NT>& c, float (&pn)[2], float4& pp) {
+    using L = GenLds<NT>;
+    if constexpr (MODE == 0) {
+        if (c.cell) {
+            pn[0] = c.lds[L::GR + c.cn * kGrW + c.cul];
+            if (c.ntc == 2) pn[1] = c.lds[L::GR + c.cn * kGrW + 16 + c.cul];
+        }
+    }
+    if (c.gcell) pp = reinterpret_cast<const float4*>(c.lds + L::P1R)[c.cn * GU + c.cul];
+}
+// fc3 epilogue (hop 2's end), from the partials in F3
+template <int MODE, bool DBG, int NT>
+__device__ __forceinline__ void gen_pub_fc3(const PersistGenArgs& a, const GenCell<NT>& c, const GenState& s,
+                                            const float (&pn)[2], int t, unsigned seq) {
+    using L = GenLds<NT>;
+    const float* cb = c.lds + L::CB;
+    if constexpr (MODE == 0) {
+        // candidate: the max key (cand_key.h cand_key, l_k + G_k formed exactly) over the
+        // slot's classes of row cn: lane cul takes classes cpw w + 16 j + cul, j < ntc
+        uint32_t kh = 0, kl = 0;
+        if (c.cell) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                if (j >= c.ntc) break;
+                const int cl = a.cpw * c.w + 16 * j + c.cul;
+                const float lg = p_add(c.psum(L::F3, 2, j, c.cul), cb[32 + 16 * j + c.cul]);
+                p_dbg_logit<DBG>(a.dbg, t, c.crow, cl, a.B, a.n_classes, lg);
+                const CandKey k = cand_key(lg, __float_as_uint(pn[j]), cl);
+                kmax_take(kh, kl, k.hi, k.lo);
+            }
+        }
+        row16_kmax(kh, kl);
+        unsigned vo = c.cell && c.cul == 0 ? g_cand(c.cnl, c.w) : kNoOff;
+        asm volatile("" : "+v"(vo));
+        __builtin_amdgcn_raw_buffer_store_b64((u2v){kh, kl | key_tag(seq)}, c.xr, vo, GX_D * 4 + c.xt, 0);
+    } else {
+        // MOL / BETA: logit 16 w + cul of row cn (slots 0 and 1) as a tagged pair (float
+        // bits, seq), polled directly in hop 3; every lane issues the store (kNoOff: dropped)
+        float lg = 0.f;
+        if (s.o_lp != kNoOff) {
+            lg = p_add(c.psum(L::F3, 2, 0, c.cul), cb[32 + c.cul]);
+            p_dbg_logit<DBG>(a.dbg, t, c.crow, 16 * c.w + c.cul, a.B, a.n_classes, lg);
+        }
+        unsigned vo = s.o_lp;
+        asm volatile("" : "+v"(vo));
+        __builtin_amdgcn_raw_buffer_store_b64((u2v){__float_as_uint(lg), seq}, c.xr, vo, GX_D * 4 + c.xt, 0);
+    }
+}
+// gh1 = W_hh1 h1 + b_hh1 of the cell's unit, from the partials in HH
+template <int NT>
+__device__ __forceinline__ void gen_gh1(const GenCell<NT>& c, float& g1r, float& g1z, float& g1n) {
+    using L = GenLds<NT>;
+    const float* cb = c.lds + L::CB;
+    g1r = g1z = g1n = 0.f;
+    if (c.gcell) {
+        g1r = p_add(c.psum(L::HH, 2, 0, c.cul), cb[c.cul]);
+        g1z = p_add(c.psum(L::HH, 2, 0, 8 + c.cul), cb[8 + c.cul]);
+        g1n = p_add(c.psum(L::HH, 2, 1, c.cul), cb[16 + c.cul]);
+    }
+}
+// ---- hop 3: the sample of step t; slot 0 stores it (BITS: with its label). Every slot forms it
+// (each needs x for its own GRU units). BITS: lane cul polls the candidates of slots 2 cul,
+// 2 cul + 1 of row cn; MOL / BETA: logits cul and 16 + cul of its row ------------------------
+template <int MODE, int NT>
+__device__ __forceinline__ float gen_sample(const PersistGenArgs& a, const GenCell<NT>& c, GenState& s, int t,
+                                            unsigned seq, bool& fail) {
+    float x;
+    if constexpr (MODE == 0) {
+        u4v q;
+        fail |= !poll_cand_couple(c.xr, c.cell, g_cand(c.cnl, 2 * c.cul), GX_D * 4 + c.xt, key_tag(seq), a.ctl,
+                                  c.wh(4), (unsigned)t, true, q);
+        uint32_t bh = c.cell ? q.x : 0u, bl = c.cell ? q.y : 0u;
+        kmax_take(bh, bl, c.cell ? q.z : 0u, c.cell ? q.w : 0u);
+        row16_kmax(bh, bl);  // the 32 slots' candidates: argmax over all classes of row cn
+        const int bi = key_cls(bl);
+        x = bits_sample_of(bi, a.n_classes);
+        if (c.w == 0 && c.cell && c.cul == 0) {
+            int nn = c.cn;
+            asm volatile("" : "+v"(nn));
+            const unsigned ro = (unsigned)((c.g0 + kPG * nn) * a.ld);
+            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u, (unsigned)t * 2u, 0);
+            bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
+        }
+    } else {
+        u2v qa, qb;
+        fail |= !poll_logit_pairs(c.xr, s.l_ra ? g_logit(c.cnl, c.cul) : kNoOff,
+                                  s.l_rb ? g_logit(c.cnl, 16 + c.cul) : kNoOff, GX_D * 4 + c.xt, s.l_ra, s.l_rb, seq,
+                                  a.ctl, c.wh(5), (unsigned)t, true, qa, qb);
+        const float la = __uint_as_float(qa.x);
+        [[maybe_unused]] const float lb = __uint_as_float(qb.x);
+        if constexpr (MODE == 2) {
+            // BETA (geneing 'RAW'): vocoder/distribution.py:7-20, Beta(exp l0, exp l1) on
+            // [-1, 1] with the Philox gamma draws: lane 0 of the row draws X ~ Gamma(exp l0),
+            // lane 1 Y ~ Gamma(exp l1) concurrently (philox.h gamma_mt, g = lane); lane 0
+            // forms 2 X / (X + Y) - 1 exactly as beta_sample and k_persist_gen do
+            const int base = c.l & 48;  // lane 0 of this lane's row
+            double gv = 0.0;
+            if (c.cell && c.cul < 2) {
+                const RowInfo& ri = c.row(c.cn);
+                gv = gamma_mt((double)expf(la), (uint32_t)c.cul, (uint32_t)t, (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
+            }
+            const double gy = __shfl(gv, base + 1);
+            float xv = 0.f;
+            {
+#pragma clang fp contract(off)
+                const float sb = (float)(gv / (gv + gy));
+                xv = 2.0f * sb - 1.0f;
+            }
+            x = __shfl(xv, base);
+        } else {
+            x = mol_sample_row16(la, lb, s.pg, c.cul, c.l);
+            s.pg = s.pgn;
+        }
+        if (c.w == 0 && c.cell && c.cul == 0) {
+            int nn = c.cn;
+            asm volatile("" : "+v"(nn));
+            bst(x, mk_rsrc(a.samples), (unsigned)((c.g0 + kPG * nn) * a.ld) * 4u, (unsigned)t * 4u);
+        }
+    }
+    return x;
+}
+// ---- GRU1 of step t + 1 for the slot's units -> x1, h1 ---------------------------------------
+//   gi = W_ih1 (cI + w0 x) + b_ih1 = P1 + v x ; x1 = (cI + w0 x) + h1
+template <int NT>
+__device__ __forceinline__ void gen_gru1_pub(const GenCell<NT>& c, GenState& s, float x, const float4& pp, float g1r,
+                                             float g1z, float g1n, unsigned seq) {
+    float x1 = 0.f;
+    if (c.gcell) {
+        s.h1r = p_gru(fmaf(s.vr, x, pp.x), fmaf(s.vz, x, pp.y), fmaf(s.vn, x, pp.z), g1r, g1z, g1n, s.h1r);
+        x1 = p_add(fmaf(s.w0c, x, pp.w), s.h1r);
+    }
+    c.pub(GX_X1, GS_X, c.o_px, x1, seq + 1u);
+    c.pub(GX_H1, GS_X, c.o_px, s.h1r, seq + 1u);
+}
+// the step's end: progress for the host's callback, and its abort (seen at the next step's check)
+template <int NT>
+__device__ __forceinline__ void gen_step_end(const PersistGenArgs& a, const GenCell<NT>& c, int t) {
+    if (c.w == 0 && threadIdx.x == 0) {
+        if (c.g == 0) p_progress(a.progress, a.prog_base, t);
+        if (p_abort(a.ctl, a.progress, t)) c.lds[GenLds<NT>::FAIL] = 1.f;
+    }
+}
 
 // Poll the lane's NP B-operand packets (1 KiB apart) until none holds the sentinel; lanes
 // without a packet (rows >= R) load from kNoOff, which reads 0. Bounded: records the first
@@ -162,539 +501,52 @@ __device__ __forceinline__ bool g_poll(rsrc_t xr, unsigned voff, unsigned so, bo
         asm volatile("" : "+v"(vo));
         cc[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, so, kCpNT);
         if constexpr (NP == 2) cc[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024u, so, kCpNT);
-        bool ok = g_ready(cc[0]);
-        if constexpr (NP == 2) ok &= g_ready(cc[1]);
+        bool ok = packet_ready(cc[0]);
+        if constexpr (NP == 2) ok &= packet_ready(cc[1]);
         if (__all((int)ok)) return true;
         if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
-            if ((threadIdx.x & 63) == 0 && !ld_sc1_u(ctl + PC_ERR) &&
-                atomicCAS(ctl + PC_WHERE, 0u, where | ((threadIdx.x >> 6) << 19)) == 0u) {
-                ctl[PC_WHERE + 1] = 1u;
-                ctl[PC_WHERE + 2] = step;
-            }
-            if ((threadIdx.x & 63) == 0) atomicMax(ctl + PC_ERR, 2u);
+            spin_give_up(ctl, where, step, true);
+            return false;
+        }
+    }
+}
+// g_poll over both tiles: the lane's NP packets of tile 0 and of tile 1 (kTile1B behind) in one
+// pass, until none holds the sentinel; bounded and recorded exactly as g_poll
+template <int NP>
+__device__ __forceinline__ bool g_poll2(rsrc_t xr, unsigned voff, unsigned so, bool valid0, bool valid1,
+                                        u4v (&c0)[2], u4v (&c1)[2], unsigned* ctl, unsigned where, unsigned step) {
+    const unsigned t0 = p_now();
+    unsigned nsp = 0;
+    while (true) {
+        unsigned vo0 = valid0 ? voff : kNoOff, vo1 = valid1 ? voff : kNoOff;
+        asm volatile("" : "+v"(vo0), "+v"(vo1));
+        c0[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo0, so, kCpNT);
+        if constexpr (NP == 2) c0[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo0 + 1024u, so, kCpNT);
+        c1[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo1, so + kTile1B, kCpNT);
+        if constexpr (NP == 2) c1[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo1 + 1024u, so + kTile1B, kCpNT);
+        bool ok = packet_ready(c0[0]);
+        ok &= packet_ready(c1[0]);
+        if constexpr (NP == 2) {
+            ok &= packet_ready(c0[1]);
+            ok &= packet_ready(c1[1]);
+        }
+        if (__all((int)ok)) return true;
+        if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
+            spin_give_up(ctl, where, step, true);
             return false;
         }
     }
 }
 
-// ---- ring instances: the slot's per-step operands, formed by waves 4-7 into the one-slot LDS
-// arrays; produced and consumed by the same workgroup only ------------------------------------
-// The Gumbel word of (tau, row n, class) as k_gumbel forms it (philox.h gumbel_q_of, keyed by
-// class quad, absolute step, fold, stream). Thread j of a row takes class j of slot w (cpw 16,
-// ntc 1) or the pair 2 j, 2 j + 1 (cpw 32, ntc 2: one Philox block for both).
-// (LRI, LGR / LP1: the LDS offsets of the RowInfo array and of the destination array -- the 32-row
-// instances, whose arrays lie elsewhere, run the same code)
-template <int LRI = WL_RI, int LGR = WL_GR>
-__device__ __forceinline__ void ring_noise_make(const PersistGenRingArgs& a, float* lds, int w, int ntc, int n,
-                                                int j, int tau) {
-    int c = a.cpw * w + (ntc == 2 ? 2 * j : j);
-    asm volatile("" : "+v"(c));
-    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + LRI)[n];
-    // (a padding row repeats the last real row: drawn and never used)
-    const U4 o = philox4x32_10((uint32_t)(c >> 2), (uint32_t)tau, (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
-    const int q = c & 3;
-    const uint32_t wd = q == 0 ? o.x : q == 1 ? o.y : q == 2 ? o.z : o.w;
-    float* dst = lds + LGR + n * kGrW + (ntc == 2 ? 2 * j : j);
-    dst[0] = __uint_as_float(gumbel_q_of(wd));
-    if (ntc == 2) {  // class c + 1 of the same quad (c is even)
-        __builtin_amdgcn_sched_barrier(0);
-        dst[1] = __uint_as_float(gumbel_q_of(q == 0 ? o.y : o.w));
-    }
-}
-// P1(tau) of (row n, unit 8 w + j) from the per-frame tables, k_p1_expand's fma chain without its
+// ---- ring instances: the slot's per-step operands, formed into the one-slot LDS arrays; produced
+// and consumed by the same workgroup only. In two parts each, so that the 32-row instances can
+// issue a step's table loads and draw its Philox words at the top of the step and form the values
+// after its second barrier; the 16-row instances (and the prologue) run both parts at once
+// (ring_p1_make, ring_noise_make) -------------------------------------------------------------
+// P1(tau) of (row ri, unit 8 w + j) from the per-frame tables, k_p1_expand's fma chain without its
 // zero tap (as kernels_persist_wide.hip p1_make): positions >= L take the zero frame at fbase
 // (bias only), frames outside the utterance its zeroed guard slots; tau is clamped at the row's
 // last step, as the stream read clamps it.
-template <int LRI = WL_RI, int LP1 = WL_P1R>
-__device__ __forceinline__ void ring_p1_make(const PersistGenRingArgs& a, float* lds, int w, int n, int j, int tau) {
-    const int tc = tau < a.S ? tau : a.S - 1;
-    int uu = GU * w + j;
-    asm volatile("" : "+v"(uu));
-    const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + LRI)[n];
-    const unsigned p = (unsigned)(ri.rel0 + tc);
-    const bool in = p < (unsigned)ri.L;  // else the zero tail pad: bias only (zero frame)
-    const unsigned f = p / (unsigned)a.hop, sph = in ? p - f * (unsigned)a.hop : 0u;
-    const unsigned s0 = in ? (unsigned)ri.fbase - 1u + f + (sph >= (unsigned)a.p1split ? 1u : 0u)
-                           : (unsigned)ri.fbase;
-    constexpr unsigned kRow = 4u * GH * 4u;  // bytes per frame slot
-    const unsigned col = (unsigned)uu * 16u;
-    const float4 tk = __builtin_bit_cast(
-        float4, __builtin_amdgcn_raw_buffer_load_b128(mk_rsrc(a.p1taps), sph * 16u, 0, 0));
-    const rsrc_t qr = mk_rsrc(a.p1q);
-    float4 tq[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        tq[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                               qr, (in ? s0 + (unsigned)k : s0) * kRow + col, 0, 0));
-    const float4 ta = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                     mk_rsrc(a.p1a), (in ? (unsigned)ri.fbase + 1u + f : s0) * kRow + col, 0, 0));
-    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float kk[4] = {tk.x, tk.y, tk.z, tk.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        m.x = fmaf(kk[k], tq[k].x, m.x);
-        m.y = fmaf(kk[k], tq[k].y, m.y);
-        m.z = fmaf(kk[k], tq[k].z, m.z);
-        m.w = fmaf(kk[k], tq[k].w, m.w);
-    }
-    reinterpret_cast<float4*>(lds + LP1)[n * GU + j] =
-        make_float4(p_add(m.x, ta.x), p_add(m.y, ta.y), p_add(m.z, ta.z), p_add(m.w, ta.w));
-}
-}  // namespace
-
-// MODE: 0 BITS (categorical), 1 MOL, 2 BETA (geneing 'RAW'); each its own instantiation (the BETA
-//       float64 gamma sampler would otherwise raise the other instances' register allocation)
-// RING: P1 (every head) and the Gumbel noise (BITS) formed in-kernel into LDS instead of read from
-//       the call's streams (MOL keeps its k_mol_noise stream). A ring instance takes
-//       PersistGenRingArgs (the per-frame tables behind the common arguments); the stream
-//       instances keep PersistGenArgs, so their code is what it was before the ring existed
-// DBG: the instance that records logits for the teacher-forced gate (wrnn_set_debug_steps)
-template <int MODE, bool RING, bool DBG>
-__global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(
-    std::conditional_t<RING, PersistGenRingArgs, PersistGenArgs> a) {
-    static_assert(MODE >= 0 && MODE <= 2, "BITS, MOL or BETA");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int* sreg = reinterpret_cast<int*>(lds + WL_REG);
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        int gg, ss;
-        sreg[2] = p_register(a.ctl, gg, ss);
-        sreg[0] = gg;
-        sreg[1] = ss;
-    }
-    __syncthreads();
-    if (!sreg[2]) return;
-    const int g = __builtin_amdgcn_readfirstlane(sreg[0]);
-    const int w = __builtin_amdgcn_readfirstlane(sreg[1]);
-    const int v = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave: K-eighth v of every product
-    const int l = tid & 63;
-    const int R = a.nr;
-    const int g0 = a.rb + g;
-    const int bn = l & 15;
-    const bool bvalid = bn < R;
-    const int cn = tid >> 4, cul = tid & 15;  // epilogue cell (row cn, tile row cul), waves 0-3
-    const bool cell = tid < 16 * R;
-    const bool gcell = cell && cul < GU;      // GRU cell: unit 8 w + cul
-    const bool fcell = cell && cul < GO;      // fc1 cell: output 4 w + cul
-    const int cu = GU * w + (cul & 7);
-    const int crow = g0 + kPG * (cell ? cn : 0);
-    const int ntc = MODE == 0 ? a.cpw / 16 : 1;  // fc3 tiles of the slot (1 or 2; MOL / BETA: 1)
-    const rsrc_t xr = mk_rsrc(a.xbuf + (size_t)g * GX_GROUP);
-    const unsigned o_cx = g_cons_x(v, l), o_cy = g_cons_y(v, l);
-    // publishing lanes: x1 / h1 the first lane of each unit quad, y1 the row's lane 0
-    const unsigned o_px = gcell && (cul & 3) == 0 ? g_prod_x(GU * w + cul, cn) : kNoOff;
-    const unsigned o_py = cell && cul == 0 ? g_prod_y(GO * w, cn) : kNoOff;
-    auto wh = [&](unsigned site) { return site << 28 | (unsigned)w << 22; };
-
-    // ---- weights: K = 256 tile T (< 3), k-step ks at wq[2 T + ks / 4] component ks % 4;
-    //      fc3 tile j, k-step ks at wq[6 + j] component ks -------------------------------------
-    float4 wq[kWgq];
-    {
-        const float4* src = a.wwide + ((size_t)(w * 8 + v) * kWgq) * 64 + l;
-#pragma unroll
-        for (int q = 0; q < kWgq; ++q) wq[q] = src[(size_t)q * 64];
-    }
-    if (tid < R) reinterpret_cast<RowInfo*>(lds + WL_RI)[tid] = a.rows[g0 + kPG * tid];
-    if (tid == 0) lds[WL_FAIL] = 0.f;
-    if (tid < 24) lds[WL_CB + tid] = a.b_hh1[(tid >> 3) * GH + GU * w + (tid & 7)];
-    if (tid >= 32 && tid < 32 + a.cpw) {
-        const int c = a.cpw * w + tid - 32;
-        lds[WL_CB + tid] = c < a.n_classes ? a.b_f3[c] : 0.f;
-    }
-
-    // publish the lane's value of step seq as one packet of its quad: slot seq & 1, the
-    // sentinel into slot (seq + 1) & 1. Every lane of the wave issues both stores (a lane that
-    // does not publish uses kNoOff, which the buffer range check drops): no branch around them,
-    // so the compiler's waits after them stay counted (DESIGN §3.0b)
-    auto pub = [&](int buf, int sz, unsigned off, float val, unsigned seq) {
-        const float u1 = pdpp<0x39>(val), u2 = pdpp<0x4E>(val), u3 = pdpp<0x93>(val);
-        unsigned vo = off;
-        asm volatile("" : "+v"(vo));
-        __builtin_amdgcn_raw_buffer_store_b128(
-            (u4v){__float_as_uint(val), __float_as_uint(u1), __float_as_uint(u2), __float_as_uint(u3)}, xr, vo,
-            g_slot(buf, sz, seq), 0);
-        __builtin_amdgcn_raw_buffer_store_b128((u4v){kSentG, kSentG, kSentG, kSentG}, xr, vo,
-                                               g_slot(buf, sz, seq + 1u), 0);
-    };
-    // partial tile j of a product into P ([v][nt][n][m], swizzled)
-    auto put = [&](int P, int NT, int j, const v4f& acc) {
-        *reinterpret_cast<v4f*>(lds + P + ((v * NT + j) * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc;
-    };
-    // the cell's sum of the 8 waves' partials of tile j, tile row m (fixed order v = 0 .. 7)
-    auto psum = [&](int P, int NT, int j, int m) {
-        float p[8];
-#pragma unroll
-        for (int vv = 0; vv < 8; ++vv) p[vv] = lds[P + ((vv * NT + j) * 16 + cn) * 16 + wsw(cn, m)];
-        float acc = 0.f;
-#pragma unroll
-        for (int vv = 0; vv < 8; ++vv) acc += p[vv];
-        return acc;
-    };
-
-    float h1r = 0.f, x1c = 0.f;
-    if (gcell) {  // x1, h1 of step 0 (k_persist_gen_init)
-        const float* st = a.st + (size_t)crow * 2 * GH;
-        x1c = st[cu];
-        h1r = st[GH + cu];
-    }
-    const float vr = gcell ? a.v[cu] : 0.f, vz = gcell ? a.v[GH + cu] : 0.f, vn = gcell ? a.v[2 * GH + cu] : 0.f;
-    const float w0c = gcell ? a.w0[cu] : 0.f;
-    const float* cb = lds + WL_CB;
-    const rsrc_t fcr = mk_rsrc(a.fcond);
-    // in-step byte offsets of the cell's stream operands (the step's base is uniform, 64-bit)
-    const unsigned o_p1 = (unsigned)((cell ? cn : 0) * kPG * 4 * GH + cu * 4) * 4u;
-    const unsigned o_gn = MODE == 1 ? (unsigned)(crow * kMolNoise + cul) * 4u
-                                    : (unsigned)(crow * a.n_classes + a.cpw * w + cul) * 4u;
-    // MOL: lane cul < kMolNoise of a row holds draw cul of its row from the k_mol_noise stream
-    // ([S][B][kMolNoise]); pg is the draw of step t, pgn the one of step t + 1 (clamped at the
-    // last step, where it goes unused)
-    [[maybe_unused]] float pg = 0.f, pgn = 0.f;
-    [[maybe_unused]] auto mol_draw = [&](int te) {
-        const int tc = te < a.S ? te : a.S - 1;
-        if (cell && cul < kMolNoise) pgn = bld(mk_rsrc(a.gumbel + (size_t)tc * a.B * kMolNoise), o_gn, 0);
-    };
-    // MOL / BETA: the lane's pair in the logit area as producer (slots 0 and 1: logit 16 w + cul)
-    // and as consumer (logits cul and 16 + cul of row cn); kNoOff where there is none
-    [[maybe_unused]] const bool l_ra = cell && cul < a.n_classes, l_rb = cell && 16 + cul < a.n_classes;
-    [[maybe_unused]] const unsigned o_lp =
-        cell && w < 2 && 16 * w + cul < a.n_classes ? g_logit(cn, 16 * w + cul) : kNoOff;
-    // ring instances: thread i of waves 4-7 forms the P1 cell (row i / 8, unit i % 8) for i < 8 R
-    // and, BITS, the noise cell (row i / 16, thread i % 16 of the row) for i < 16 R (ring_p1_make,
-    // ring_noise_make above) into the one-slot LDS arrays
-    [[maybe_unused]] auto ring_make = [&](const PersistGenRingArgs& ra, int t_noise, int t_p1) {
-        const int i = tid - 256;
-        if (i < GU * R) ring_p1_make(ra, lds, w, i >> 3, i & 7, t_p1);
-        if constexpr (MODE == 0)
-            if (i < 16 * R) ring_noise_make(ra, lds, w, ntc, i >> 4, i & 15, t_noise);
-    };
-    __syncthreads();
-    // ring prologue: the noise of step t0 and P1(t0 + 1) (step t forms the noise of t + 1 and
-    // P1(t + 2)); waves 0-3 read them after step t0's first barrier
-    if constexpr (RING)
-        if (v >= 4) ring_make(a, a.t0, a.t0 + 1);
-    if constexpr (MODE == 1) {  // the draws of step t0 (the loop loads those of t + 1 at step t)
-        mol_draw(a.t0);
-        pg = pgn;
-    }
-    // initial x1, h1 (canonicalised: a signalling NaN in a carried state must not read as the
-    // sentinel), as step t0's vectors
-    if (v < 4) {
-        pub(GX_X1, GS_X, o_px, __builtin_canonicalizef(x1c), (unsigned)a.t0 + 1u);
-        pub(GX_H1, GS_X, o_px, __builtin_canonicalizef(h1r), (unsigned)a.t0 + 1u);
-    }
-    bool fail = false;
-    u4v cc[2];
-    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[0] = p_now();
-    for (int t = a.t0; t < a.t1; ++t) {
-        const unsigned seq = (unsigned)t + 1u;
-        // ---- per-step cell operands: fc1 conditioning of frame(t), the noise of step t, P1 of
-        // step t + 1 (clamped at the last step, where its GRU1 goes unused) ------------------
-        float pc = 0.f;
-        [[maybe_unused]] float pn[2] = {0.f, 0.f};
-        float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (fcell) {
-            const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[cn];
-            pc = bld(fcr, (unsigned)(p_frame(ri, t, a.hop) * a.cond_width + a.oF1 + GO * w + cul) * 4u, 0);
-        }
-        // (ring instances: pn and pp come from the LDS arrays after this step's first barrier)
-        if constexpr (MODE == 0 && !RING) {
-            if (cell) {
-                const rsrc_t nr_ = mk_rsrc(a.gumbel + (size_t)t * a.B * a.n_classes);
-                pn[0] = bld(nr_, o_gn, 0);
-                if (ntc == 2) pn[1] = bld(nr_, o_gn + 64u, 0);
-            }
-        } else if constexpr (MODE == 1) {
-            mol_draw(t + 1);
-        }
-        if constexpr (!RING) {
-            if (gcell) {
-                const int tn = t + 1 < a.S ? t + 1 : t;
-                pp = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                    mk_rsrc(a.P1 + ((size_t)tn * a.B + g0) * 4 * GH), o_p1, 0, 0));
-            }
-        }
-        // ---- hop 1: x1 of every slot -> fc1 -> y1 -------------------------------------------
-        fail |= !g_poll<2>(xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid, cc, a.ctl, wh(1), (unsigned)t);
-        {
-            v4f acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) acc = mfma4(f4c(wq[4 + ks / 4], ks % 4), u4c(cc[ks >> 2], ks & 3), acc);
-            put(WP_F1, 1, 0, acc);
-        }
-        if (fail) lds[WL_FAIL] = 1.f;
-        gbar();
-        if (lds[WL_FAIL] != 0.f) return;
-        if (v < 4) {
-            float y = 0.f;
-            if (fcell) {
-                y = p_add(psum(WP_F1, 1, 0, cul), pc);
-                y = y > 0.f ? y : 0.f;
-            }
-            pub(GX_Y1, GS_Y, o_py, y, seq);
-            if constexpr (RING) {
-                // the slot's noise of step t and P1(t + 1): written by waves 4-7 before the barrier
-                // above (step t - 1's tail, or the prologue), overwritten only after the barrier
-                // below
-                if constexpr (MODE == 0) {
-                    if (cell) {
-                        pn[0] = lds[WL_GR + cn * kGrW + cul];
-                        if (ntc == 2) pn[1] = lds[WL_GR + cn * kGrW + 16 + cul];
-                    }
-                }
-                if (gcell) pp = reinterpret_cast<const float4*>(lds + WL_P1R)[cn * GU + cul];
-            }
-        }
-        // ---- in the wait for y1: h1 of every slot -> W_hh1 h1 (GRU1 at this step's end) ------
-        fail |= !g_poll<2>(xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid, cc, a.ctl, wh(2), (unsigned)t);
-        {
-            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const float b = u4c(cc[ks >> 2], ks & 3);
-                a0 = mfma4(f4c(wq[ks / 4], ks % 4), b, a0);
-                a1 = mfma4(f4c(wq[2 + ks / 4], ks % 4), b, a1);
-            }
-            put(WP_HH, 2, 0, a0);
-            put(WP_HH, 2, 1, a1);
-        }
-        // ---- hop 2: y1 of every slot -> fc3 -> the slot's candidate of every row ------------
-        // (MOL / BETA: one tile; slots 2-31, for BETA 1-31, run it on their zero image, so every
-        // slot polls y1 at every step as in BITS and the sentinel protocol of y1 is unchanged)
-        fail |= !g_poll<1>(xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid, cc, a.ctl, wh(3), (unsigned)t);
-        {
-            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const float b = u4c(cc[0], ks);
-                a0 = mfma4(f4c(wq[6], ks), b, a0);
-                if (ntc == 2) a1 = mfma4(f4c(wq[7], ks), b, a1);
-            }
-            put(WP_F3, 2, 0, a0);
-            if (ntc == 2) put(WP_F3, 2, 1, a1);
-        }
-        if (fail) lds[WL_FAIL] = 1.f;
-        gbar();
-        if (v < 4) {
-            [[maybe_unused]] const unsigned want = key_tag(seq);
-            float g1r = 0.f, g1z = 0.f, g1n = 0.f;
-            if constexpr (MODE == 0) {
-                // candidate: the max key (cand_key.h cand_key, l_k + G_k formed exactly) over the
-                // slot's classes of row cn: lane cul takes classes cpw w + 16 j + cul, j < ntc
-                uint32_t kh = 0, kl = 0;
-                if (cell) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        if (j >= ntc) break;
-                        const int c = a.cpw * w + 16 * j + cul;
-                        const float lg = p_add(psum(WP_F3, 2, j, cul), cb[32 + 16 * j + cul]);
-                        p_dbg_logit<DBG>(a.dbg, t, crow, c, a.B, a.n_classes, lg);
-                        const CandKey k = cand_key(lg, __float_as_uint(pn[j]), c);
-                        kmax_take(kh, kl, k.hi, k.lo);
-                    }
-                }
-                row16_kmax(kh, kl);
-                unsigned vo = cell && cul == 0 ? g_cand(cn, w) : kNoOff;
-                asm volatile("" : "+v"(vo));
-                __builtin_amdgcn_raw_buffer_store_b64((u2v){kh, kl | want}, xr, vo, GX_D * 4, 0);
-            } else {
-                // MOL / BETA: logit 16 w + cul of row cn (slots 0 and 1) as a tagged pair (float
-                // bits, seq), polled directly in hop 3; every lane issues the store (kNoOff: dropped)
-                float lg = 0.f;
-                if (o_lp != kNoOff) {
-                    lg = p_add(psum(WP_F3, 2, 0, cul), cb[32 + cul]);
-                    p_dbg_logit<DBG>(a.dbg, t, crow, 16 * w + cul, a.B, a.n_classes, lg);
-                }
-                unsigned vo = o_lp;
-                asm volatile("" : "+v"(vo));
-                __builtin_amdgcn_raw_buffer_store_b64((u2v){__float_as_uint(lg), seq}, xr, vo, GX_D * 4, 0);
-            }
-            if (gcell) {  // gh1 = W_hh1 h1 + b_hh1 of the cell's unit
-                g1r = p_add(psum(WP_HH, 2, 0, cul), cb[cul]);
-                g1z = p_add(psum(WP_HH, 2, 0, 8 + cul), cb[8 + cul]);
-                g1n = p_add(psum(WP_HH, 2, 1, cul), cb[16 + cul]);
-            }
-            // ---- hop 3: sample of step t (lane cul polls slots 2 cul, 2 cul + 1 of row cn) ----
-            float x;
-            if constexpr (MODE == 0) {
-                u4v q = {0u, want, 0u, want};
-                const unsigned t0s = p_now();
-                unsigned nsp = 0;
-                while (true) {
-                    if (cell) {
-                        unsigned vo = g_cand(cn, 2 * cul);
-                        asm volatile("" : "+v"(vo));
-                        q = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, GX_D * 4, kCpNT);
-                    }
-                    if (__all(((q.y & kKeyTagMask) == want) & ((q.w & kKeyTagMask) == want))) break;
-                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
-                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
-                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(4) | ((unsigned)v << 19)) == 0u) {
-                            a.ctl[PC_WHERE + 1] = 1u;
-                            a.ctl[PC_WHERE + 2] = (unsigned)t;
-                        }
-                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
-                        fail = true;
-                        break;
-                    }
-                }
-                uint32_t bh = cell ? q.x : 0u, bl = cell ? q.y : 0u;
-                kmax_take(bh, bl, cell ? q.z : 0u, cell ? q.w : 0u);
-                row16_kmax(bh, bl);  // the 32 slots' candidates: argmax over all classes of row cn
-                const int bi = key_cls(bl);
-                {
-#pragma clang fp contract(off)
-                    x = (2.0f * (float)bi) / (float)(a.n_classes - 1) - 1.0f;
-                }
-                if (w == 0 && cell && cul == 0) {
-                    int nn = cn;
-                    asm volatile("" : "+v"(nn));
-                    const unsigned ro = (unsigned)((g0 + kPG * nn) * a.ld);
-                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u,
-                                                          (unsigned)t * 2u, 0);
-                    bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
-                }
-            } else {
-                // lane (row cn, cul) polls logits cul and 16 + cul of its row (tag: the whole seq);
-                // a lane without a logit loads from kNoOff (reads 0, not waited for)
-                unsigned va = l_ra ? g_logit(cn, cul) : kNoOff;
-                unsigned vb = l_rb ? g_logit(cn, 16 + cul) : kNoOff;
-                asm volatile("" : "+v"(va), "+v"(vb));
-                u2v qa, qb;
-                const unsigned t0s = p_now();
-                unsigned nsp = 0;
-                while (true) {
-                    qa = __builtin_amdgcn_raw_buffer_load_b64(xr, va, GX_D * 4, kCpNT);
-                    qb = __builtin_amdgcn_raw_buffer_load_b64(xr, vb, GX_D * 4, kCpNT);
-                    if (__all((!l_ra | (qa.y == seq)) & (!l_rb | (qb.y == seq)))) break;
-                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
-                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
-                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(5) | ((unsigned)v << 19)) == 0u) {
-                            a.ctl[PC_WHERE + 1] = 1u;
-                            a.ctl[PC_WHERE + 2] = (unsigned)t;
-                        }
-                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
-                        fail = true;
-                        break;
-                    }
-                }
-                const float la = __uint_as_float(qa.x);
-                [[maybe_unused]] const float lb = __uint_as_float(qb.x);
-                const int base = l & 48;  // lane 0 of this lane's row
-                if constexpr (MODE == 2) {
-                    // BETA (geneing 'RAW'): vocoder/distribution.py:7-20, Beta(exp l0, exp l1) on
-                    // [-1, 1] with the Philox gamma draws: lane 0 of the row draws X ~ Gamma(exp l0),
-                    // lane 1 Y ~ Gamma(exp l1) concurrently (philox.h gamma_mt, g = lane); lane 0
-                    // forms 2 X / (X + Y) - 1 exactly as beta_sample and k_persist_gen do
-                    double gv = 0.0;
-                    if (cell && cul < 2) {
-                        const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + WL_RI)[cn];
-                        gv = gamma_mt((double)expf(la), (uint32_t)cul, (uint32_t)t, (uint32_t)ri.fold, ri.stream,
-                                      a.k0, a.k1);
-                    }
-                    const double gy = __shfl(gv, base + 1);
-                    float xv = 0.f;
-                    {
-#pragma clang fp contract(off)
-                        const float sb = (float)(gv / (gv + gy));
-                        xv = 2.0f * sb - 1.0f;
-                    }
-                    x = __shfl(xv, base);
-                } else {
-                    // MOL: k_persist_gen's operations in its order (kernels_persist_gen.hip, "MOL:";
-                    // vocoder/distribution.py:104-140)
-                    float bv;
-                    {
-#pragma clang fp contract(off)
-                        bv = cul < 10 ? la - pg : -INFINITY;
-                    }
-                    int bi = cul < 10 ? cul : 0x7fffffff;
-                    row16_argmax(bv, bi);  // first max over k < 10; every lane of the row gets it
-                    bi = bi < 10 ? bi : 0;
-                    // l[10 + bi]: the first value of lane 10 + bi, or the second of lane bi - 6
-                    const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
-                    const float mean = bi < 6 ? m0 : m1;
-                    float ls = __shfl(lb, base + 4 + bi);  // l[20 + bi]: the second value of lane 4 + bi
-                    const float lu = __shfl(pg, base + 10);
-                    {
-#pragma clang fp contract(off)
-                        const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
-                        ls = ls < lsmin ? lsmin : ls;
-                        x = mean + expf(ls) * lu;
-                        x = x < -1.f ? -1.f : x;
-                        x = x > 1.f ? 1.f : x;
-                    }
-                    pg = pgn;
-                }
-                if (w == 0 && cell && cul == 0) {
-                    int nn = cn;
-                    asm volatile("" : "+v"(nn));
-                    bst(x, mk_rsrc(a.samples), (unsigned)((g0 + kPG * nn) * a.ld) * 4u, (unsigned)t * 4u);
-                }
-            }
-            if (fail) lds[WL_FAIL] = 1.f;  // seen by every wave at the next step's check
-            // ---- GRU1 of step t + 1 for the slot's units -> x1, h1 ---------------------------
-            //   gi = W_ih1 (cI + w0 x) + b_ih1 = P1 + v x ; x1 = (cI + w0 x) + h1
-            float x1 = 0.f;
-            if (gcell) {
-                h1r = p_gru(fmaf(vr, x, pp.x), fmaf(vz, x, pp.y), fmaf(vn, x, pp.z), g1r, g1z, g1n, h1r);
-                x1 = p_add(fmaf(w0c, x, pp.w), h1r);
-            }
-            pub(GX_X1, GS_X, o_px, x1, seq + 1u);
-            pub(GX_H1, GS_X, o_px, h1r, seq + 1u);
-        } else if constexpr (RING) {
-            // waves 4-7: the noise of step t + 1 and P1(t + 2) into the one-slot LDS arrays, while
-            // waves 0-3 run the fc3 epilogue, hop 3 and GRU1 (they read the step-t values before
-            // the barrier above and read the new ones after the next step's first barrier)
-            ring_make(a, t + 1, t + 2);
-        }
-        if (w == 0 && tid == 0) {
-            if (g == 0) p_progress(a.progress, a.prog_base, t);
-            if (p_abort(a.ctl, a.progress, t)) lds[WL_FAIL] = 1.f;  // seen at the next step's check
-        }
-    }
-    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
-}
-
-// ---- 32-row ring instances ------------------------------------------------------------------
-// Up to 32 rows per XCD group in one launch: rows 0-15 of a group are MFMA column tile 0, rows
-// 16-31 column tile 1. Every wave polls both tiles' B-operand packets and runs each product for
-// both tiles on the same weight registers (two independent accumulator chains); the epilogue
-// cells of tile 0 lie on waves 0-3, those of tile 1 on waves 4-7, one cell per lane in the
-// (cn, cul) layout of a tile. A row's arithmetic is the 16-row ring instance's: the same weight
-// registers, the same K split over the 8 waves, the same fixed-order sum of the 8 partials, the
-// same epilogue, ring_p1_make / ring_noise_make and sampling code, so its outputs are the
-// 16-row instance's bit for bit. Ring form only (no stream instance).
-//
-// Exchange: tile 1 has its own copy of the whole per-group area (x1 / h1 / y1 parity slots and the
-// candidate / logit-pair area) kTile1B bytes behind tile 0's, so the offset functions above serve
-// both tiles; a group's area is 2 GX_GROUP floats. LDS: the partial buffers, the ring arrays and
-// the RowInfo array are twice the 16-row kernel's (W2_*).
-//
-// Ring work: waves 4-7 have no free tail here, so each wave set forms its own tile's next noise /
-// P1 in two parts. At the top of a step, before the hop-1 poll, a thread issues the table loads of
-// its P1 cell (their addresses depend only on t and the row; in flight over the whole step) and
-// forms the Philox words and the first Gumbel word of its noise cell in the wait for x1. After it
-// has published its fc3 candidates (logits) and before it polls the candidates of hop 3 -- in the
-// flight time of that exchange -- it forms the second Gumbel word and the P1 value and writes both
-// cells. The order is kept by the same two barriers: the arrays are read after a step's first
-// barrier and written after its second.
-namespace {
-constexpr int kRows32 = 2 * kRowsW;
-constexpr unsigned kTile1B = (unsigned)GX_GROUP * 4u;  // byte offset of tile 1's copy in a group's area
-constexpr int GX_GROUP32 = 2 * GX_GROUP;
-constexpr int W2_RI = 0;  // RowInfo of the group's rows (6 words each)
-constexpr int W2_FAIL = kRows32 * 6, W2_REG = W2_FAIL + 4, W2_CB = W2_REG + 12;
-constexpr int W2_P = 512;  // partial tiles [tile][8 v][nt][16 n][16 m], one buffer per product
-constexpr int W2P_F1 = W2_P, W2P_HH = W2P_F1 + 2 * WT, W2P_F3 = W2P_HH + 4 * WT;
-constexpr int W2_P1R = W2P_F3 + 4 * WT, W2_GR = W2_P1R + kRows32 * GU * 4, W2_TOTAL = W2_GR + kRows32 * kGrW;
-static_assert(W2_CB + 32 + 32 <= W2_P && W2_REG % 4 == 0, "slot constants overflow");
-static_assert(W2_P % 4 == 0 && W2_P1R % 4 == 0 && WT % 4 == 0, "partial tiles and P1 array: float4-aligned");
-static_assert(W2_TOTAL * sizeof(float) <= 160 * 1024, "LDS of the 32-row instances exceeds 160 KiB");
-static_assert(kTile1B % 16 == 0, "tile 1's copy: 16-byte aligned");
-
-// ring_p1_make and ring_noise_make in two parts each, the same operations in the same order: the
-// 32-row instances issue a step's table loads and draw its Philox words at the top of the step
-// before, and form the values after that step's second barrier (k_persist_wide_gen32)
 struct RingP1Taps {
     float4 tk, tq[4], ta;
 };
@@ -731,7 +583,11 @@ __device__ __forceinline__ float4 ring_p1_finish(const RingP1Taps& o) {
     }
     return make_float4(p_add(m.x, o.ta.x), p_add(m.y, o.ta.y), p_add(m.z, o.ta.z), p_add(m.w, o.ta.w));
 }
-// the Philox words of the thread's class (wd) and, ntc 2, of class c + 1 of the same quad (wd1)
+// The Gumbel word of (tau, row ri, class) as k_gumbel forms it (philox.h gumbel_q_of, keyed by
+// class quad, absolute step, fold, stream). Thread j of a row takes class j of slot w (cpw 16,
+// ntc 1) or the pair 2 j, 2 j + 1 (cpw 32, ntc 2: one Philox block for both): the Philox words of
+// the thread's class (wd) and, ntc 2, of class c + 1 of the same quad (wd1; c is even)
+// (a padding row repeats the last real row: drawn and never used)
 __device__ __forceinline__ void ring_noise_words(const PersistGenRingArgs& a, const RowInfo& ri, int w, int ntc, int j,
                                                  int tau, uint32_t& wd, uint32_t& wd1) {
     int c = a.cpw * w + (ntc == 2 ? 2 * j : j);
@@ -741,185 +597,249 @@ __device__ __forceinline__ void ring_noise_words(const PersistGenRingArgs& a, co
     wd = q == 0 ? o.x : q == 1 ? o.y : q == 2 ? o.z : o.w;
     wd1 = q == 0 ? o.y : o.w;
 }
-
-// g_poll over both tiles: the lane's NP packets of tile 0 and of tile 1 (kTile1B behind) in one
-// pass, until none holds the sentinel; bounded and recorded exactly as g_poll
-template <int NP>
-__device__ __forceinline__ bool g_poll2(rsrc_t xr, unsigned voff, unsigned so, bool valid0, bool valid1,
-                                        u4v (&c0)[2], u4v (&c1)[2], unsigned* ctl, unsigned where, unsigned step) {
-    const unsigned t0 = p_now();
-    unsigned nsp = 0;
-    while (true) {
-        unsigned vo0 = valid0 ? voff : kNoOff, vo1 = valid1 ? voff : kNoOff;
-        asm volatile("" : "+v"(vo0), "+v"(vo1));
-        c0[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo0, so, kCpNT);
-        if constexpr (NP == 2) c0[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo0 + 1024u, so, kCpNT);
-        c1[0] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo1, so + kTile1B, kCpNT);
-        if constexpr (NP == 2) c1[1] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo1 + 1024u, so + kTile1B, kCpNT);
-        bool ok = g_ready(c0[0]);
-        ok &= g_ready(c1[0]);
-        if constexpr (NP == 2) {
-            ok &= g_ready(c0[1]);
-            ok &= g_ready(c1[1]);
-        }
-        if (__all((int)ok)) return true;
-        if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
-            if ((threadIdx.x & 63) == 0 && !ld_sc1_u(ctl + PC_ERR) &&
-                atomicCAS(ctl + PC_WHERE, 0u, where | ((threadIdx.x >> 6) << 19)) == 0u) {
-                ctl[PC_WHERE + 1] = 1u;
-                ctl[PC_WHERE + 2] = step;
-            }
-            if ((threadIdx.x & 63) == 0) atomicMax(ctl + PC_ERR, 2u);
-            return false;
-        }
+// where thread j of row n writes its Gumbel words
+template <class L>
+__device__ __forceinline__ float* ring_noise_dst(float* lds, int ntc, int n, int j) {
+    return lds + L::GR + n * kGrW + (ntc == 2 ? 2 * j : j);
+}
+template <class L>
+__device__ __forceinline__ void ring_noise_make(const PersistGenRingArgs& a, float* lds, int w, int ntc, int n, int j,
+                                                int tau) {
+    uint32_t wd, wd1;
+    ring_noise_words(a, reinterpret_cast<const RowInfo*>(lds + L::RI)[n], w, ntc, j, tau, wd, wd1);
+    float* dst = ring_noise_dst<L>(lds, ntc, n, j);
+    dst[0] = __uint_as_float(gumbel_q_of(wd));
+    if (ntc == 2) {
+        __builtin_amdgcn_sched_barrier(0);
+        dst[1] = __uint_as_float(gumbel_q_of(wd1));
     }
 }
-
+template <class L>
+__device__ __forceinline__ void ring_p1_make(const PersistGenRingArgs& a, float* lds, int w, int n, int j, int tau) {
+    RingP1Taps taps;
+    ring_p1_load(a, reinterpret_cast<const RowInfo*>(lds + L::RI)[n], w, j, tau, taps);
+    reinterpret_cast<float4*>(lds + L::P1R)[n * GU + j] = ring_p1_finish(taps);
+}
 }  // namespace
 
+// MODE: 0 BITS (categorical), 1 MOL, 2 BETA (geneing 'RAW'); each its own instantiation (the BETA
+//       float64 gamma sampler would otherwise raise the other instances' register allocation)
+// RING: P1 (every head) and the Gumbel noise (BITS) formed in-kernel into LDS instead of read from
+//       the call's streams (MOL keeps its k_mol_noise stream). A ring instance takes
+//       PersistGenRingArgs (the per-frame tables behind the common arguments); the stream
+//       instances keep PersistGenArgs, so their code is what it was before the ring existed
+// DBG: the instance that records logits for the teacher-forced gate (wrnn_set_debug_steps)
+template <int MODE, bool RING, bool DBG>
+__global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(
+    std::conditional_t<RING, PersistGenRingArgs, PersistGenArgs> a) {
+    static_assert(MODE >= 0 && MODE <= 2, "BITS, MOL or BETA");
+    using L = GenLds<1>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int g, w;
+    if (!gen_register<L>(a.ctl, lds, g, w)) return;
+    const int tid = threadIdx.x;
+    const GenCell<1> c = gen_cell<MODE, 1>(a, lds, g, w);
+    const int v = c.v;
+    const bool bvalid = c.bn < c.R;
+    const unsigned o_cx = g_cons_x(v, c.l), o_cy = g_cons_y(v, c.l);
+    float4 wq[kWgq];
+    gen_load_weights(a, c, wq);
+    gen_setup_lds(a, c);
+    GenState s = gen_state(a, c);
+    const rsrc_t fcr = mk_rsrc(a.fcond);
+    // stream instances: in-step byte offsets of the cell's stream operands (the step's base is
+    // uniform, 64-bit)
+    [[maybe_unused]] const unsigned o_p1 = (unsigned)((c.cell ? c.cn : 0) * kPG * 4 * GH + c.cu * 4) * 4u;
+    [[maybe_unused]] const unsigned o_gn = (unsigned)(c.crow * a.n_classes + a.cpw * w + c.cul) * 4u;
+    // ring instances: thread i of waves 4-7 forms the P1 cell (row i / 8, unit i % 8) for i < 8 R
+    // and, BITS, the noise cell (row i / 16, thread i % 16 of the row) for i < 16 R into the
+    // one-slot LDS arrays
+    [[maybe_unused]] auto ring_make = [&](const PersistGenRingArgs& ra, int t_noise, int t_p1) {
+        const int i = tid - 256;
+        if (i < GU * c.R) ring_p1_make<L>(ra, lds, w, i >> 3, i & 7, t_p1);
+        if constexpr (MODE == 0)
+            if (i < 16 * c.R) ring_noise_make<L>(ra, lds, w, c.ntc, i >> 4, i & 15, t_noise);
+    };
+    __syncthreads();
+    // ring prologue: the noise of step t0 and P1(t0 + 1) (step t forms the noise of t + 1 and
+    // P1(t + 2)); waves 0-3 read them after step t0's first barrier
+    if constexpr (RING)
+        if (v >= 4) ring_make(a, a.t0, a.t0 + 1);
+    if constexpr (MODE == 1) {  // the draws of step t0 (the loop loads those of t + 1 at step t)
+        gen_mol_draw(a, c, s, a.t0);
+        s.pg = s.pgn;
+    }
+    if (v < 4) gen_pub_initial(a, c, s);
+    bool fail = false;
+    u4v cc[2];
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[0] = p_now();
+    for (int t = a.t0; t < a.t1; ++t) {
+        const unsigned seq = (unsigned)t + 1u;
+        // ---- per-step cell operands: fc1 conditioning of frame(t), the noise of step t, P1 of
+        // step t + 1 (clamped at the last step, where its GRU1 goes unused) ------------------
+        const float pc = gen_fc1_cond(a, c, fcr, t);
+        [[maybe_unused]] float pn[2] = {0.f, 0.f};
+        float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
+        // (ring instances: pn and pp come from the LDS arrays after this step's first barrier)
+        if constexpr (MODE == 0 && !RING) {
+            if (c.cell) {
+                const rsrc_t nr_ = mk_rsrc(a.gumbel + (size_t)t * a.B * a.n_classes);
+                pn[0] = bld(nr_, o_gn, 0);
+                if (c.ntc == 2) pn[1] = bld(nr_, o_gn + 64u, 0);
+            }
+        } else if constexpr (MODE == 1) {
+            gen_mol_draw(a, c, s, t + 1);
+        }
+        if constexpr (!RING) {
+            if (c.gcell) {
+                const int tn = t + 1 < a.S ? t + 1 : t;
+                pp = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                    mk_rsrc(a.P1 + ((size_t)tn * a.B + c.g0) * 4 * GH), o_p1, 0, 0));
+            }
+        }
+        // ---- hop 1: x1 of every slot -> fc1 -> y1 -------------------------------------------
+        fail |= !g_poll<2>(c.xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid, cc, a.ctl, c.wh(1), (unsigned)t);
+        {
+            v4f acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) acc = mfma4(f4c(wq[4 + ks / 4], ks % 4), u4c(cc[ks >> 2], ks & 3), acc);
+            c.put(L::F1, 1, 0, 0, acc);
+        }
+        if (fail) lds[L::FAIL] = 1.f;
+        lds_barrier();
+        if (lds[L::FAIL] != 0.f) return;
+        if (v < 4) {
+            gen_pub_y1(c, pc, seq);
+            if constexpr (RING) gen_ring_read<MODE>(c, pn, pp);
+        }
+        // ---- in the wait for y1: h1 of every slot -> W_hh1 h1 (GRU1 at this step's end) ------
+        fail |= !g_poll<2>(c.xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid, cc, a.ctl, c.wh(2), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const float b = u4c(cc[ks >> 2], ks & 3);
+                a0 = mfma4(f4c(wq[ks / 4], ks % 4), b, a0);
+                a1 = mfma4(f4c(wq[2 + ks / 4], ks % 4), b, a1);
+            }
+            c.put(L::HH, 2, 0, 0, a0);
+            c.put(L::HH, 2, 0, 1, a1);
+        }
+        // ---- hop 2: y1 of every slot -> fc3 -> the slot's candidate of every row ------------
+        // (MOL / BETA: one tile; slots 2-31, for BETA 1-31, run it on their zero image, so every
+        // slot polls y1 at every step as in BITS and the sentinel protocol of y1 is unchanged)
+        fail |= !g_poll<1>(c.xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid, cc, a.ctl, c.wh(3), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const float b = u4c(cc[0], ks);
+                a0 = mfma4(f4c(wq[6], ks), b, a0);
+                if (c.ntc == 2) a1 = mfma4(f4c(wq[7], ks), b, a1);
+            }
+            c.put(L::F3, 2, 0, 0, a0);
+            if (c.ntc == 2) c.put(L::F3, 2, 0, 1, a1);
+        }
+        if (fail) lds[L::FAIL] = 1.f;
+        lds_barrier();
+        if (v < 4) {
+            float g1r, g1z, g1n;
+            gen_pub_fc3<MODE, DBG>(a, c, s, pn, t, seq);
+            gen_gh1(c, g1r, g1z, g1n);
+            const float x = gen_sample<MODE>(a, c, s, t, seq, fail);
+            if (fail) lds[L::FAIL] = 1.f;  // seen by every wave at the next step's check
+            gen_gru1_pub(c, s, x, pp, g1r, g1z, g1n, seq);
+        } else if constexpr (RING) {
+            // waves 4-7: the noise of step t + 1 and P1(t + 2) into the one-slot LDS arrays, while
+            // waves 0-3 run the fc3 epilogue, hop 3 and GRU1 (they read the step-t values before
+            // the barrier above and read the new ones after the next step's first barrier)
+            ring_make(a, t + 1, t + 2);
+        }
+        gen_step_end(a, c, t);
+    }
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
+}
+
+// ---- 32-row ring instances ------------------------------------------------------------------
+// Up to 32 rows per XCD group in one launch: rows 0-15 of a group are MFMA column tile 0, rows
+// 16-31 column tile 1. Every wave polls both tiles' B-operand packets and runs each product for
+// both tiles on the same weight registers (two independent accumulator chains); the epilogue
+// cells of tile 0 lie on waves 0-3, those of tile 1 on waves 4-7, one cell per lane in the
+// (cn, cul) layout of a tile. A row's arithmetic is the 16-row ring instance's: the same weight
+// registers, the same K split over the 8 waves, the same fixed-order sum of the 8 partials, and
+// the same step pieces (gen_*, ring_*), so its outputs are the 16-row instance's bit for bit.
+// Ring form only (no stream instance).
+//
+// Exchange: tile 1 has its own copy of the whole per-group area (x1 / h1 / y1 parity slots and the
+// candidate / logit-pair area) kTile1B bytes behind tile 0's, so the offset functions above serve
+// both tiles; a group's area is 2 GX_GROUP floats. LDS: the partial buffers, the ring arrays and
+// the RowInfo array are twice the 16-row kernel's (GenLds<2>).
+//
+// Ring work: waves 4-7 have no free tail here, so each wave set forms its own tile's next noise /
+// P1 in two parts. At the top of a step, before the hop-1 poll, a thread issues the table loads of
+// its P1 cell (their addresses depend only on t and the row; in flight over the whole step) and
+// forms the Philox words and the first Gumbel word of its noise cell in the wait for x1. After it
+// has published its fc3 candidates (logits) and before it polls the candidates of hop 3 -- in the
+// flight time of that exchange -- it forms the second Gumbel word and the P1 value and writes both
+// cells. The order is kept by the same two barriers: the arrays are read after a step's first
+// barrier and written after its second.
 template <int MODE, bool DBG>
 __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen32(PersistGenRingArgs a) {
     static_assert(MODE >= 0 && MODE <= 2, "BITS, MOL or BETA");
+    using L = GenLds<2>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    int* sreg = reinterpret_cast<int*>(lds + W2_REG);
+    int g, w;
+    if (!gen_register<L>(a.ctl, lds, g, w)) return;
     const int tid = threadIdx.x;
-    if (tid == 0) {
-        int gg, ss;
-        sreg[2] = p_register(a.ctl, gg, ss);
-        sreg[0] = gg;
-        sreg[1] = ss;
-    }
-    __syncthreads();
-    if (!sreg[2]) return;
-    const int g = __builtin_amdgcn_readfirstlane(sreg[0]);
-    const int w = __builtin_amdgcn_readfirstlane(sreg[1]);
-    const int v = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave: K-eighth v of every product
-    const int tt = v >> 2;                                   // ... and the tile of its epilogue cells
-    const int l = tid & 63;
-    const int R = a.nr;
-    const int g0 = a.rb + g;
-    const int bn = l & 15;
-    const bool bvalid0 = bn < R, bvalid1 = kRowsW + bn < R;
-    // epilogue cell (row cn of the group = column cnl of tile tt, tile row cul)
-    const int cn = tid >> 4, cnl = cn & 15, cul = tid & 15;
-    const bool cell = cn < R;
-    const bool gcell = cell && cul < GU;      // GRU cell: unit 8 w + cul
-    const bool fcell = cell && cul < GO;      // fc1 cell: output 4 w + cul
-    const int cu = GU * w + (cul & 7);
-    const int crow = g0 + kPG * (cell ? cn : 0);
-    const int ntc = MODE == 0 ? a.cpw / 16 : 1;  // fc3 tiles of the slot (1 or 2; MOL / BETA: 1)
-    const rsrc_t xr = mk_rsrc(a.xbuf + (size_t)g * GX_GROUP32);
-    const unsigned xt = (unsigned)tt * kTile1B;  // the cell's tile copy (uniform)
-    const unsigned o_cx = g_cons_x(v, l), o_cy = g_cons_y(v, l);
-    const unsigned o_px = gcell && (cul & 3) == 0 ? g_prod_x(GU * w + cul, cnl) : kNoOff;
-    const unsigned o_py = cell && cul == 0 ? g_prod_y(GO * w, cnl) : kNoOff;
-    auto wh = [&](unsigned site) { return site << 28 | (unsigned)w << 22; };
-
+    const GenCell<2> c = gen_cell<MODE, 2>(a, lds, g, w);
+    const int v = c.v;
+    const bool bvalid0 = c.bn < c.R, bvalid1 = kRowsW + c.bn < c.R;
+    const unsigned o_cx = g_cons_x(v, c.l), o_cy = g_cons_y(v, c.l);
     float4 wq[kWgq];  // (the 16-row kernel's image and register assignment)
-    {
-        const float4* src = a.wwide + ((size_t)(w * 8 + v) * kWgq) * 64 + l;
-#pragma unroll
-        for (int q = 0; q < kWgq; ++q) wq[q] = src[(size_t)q * 64];
-    }
-    const RowInfo* rinfo = reinterpret_cast<const RowInfo*>(lds + W2_RI);
-    if (tid < R) reinterpret_cast<RowInfo*>(lds + W2_RI)[tid] = a.rows[g0 + kPG * tid];
-    if (tid == 0) lds[W2_FAIL] = 0.f;
-    if (tid < 24) lds[W2_CB + tid] = a.b_hh1[(tid >> 3) * GH + GU * w + (tid & 7)];
-    if (tid >= 32 && tid < 32 + a.cpw) {
-        const int c = a.cpw * w + tid - 32;
-        lds[W2_CB + tid] = c < a.n_classes ? a.b_f3[c] : 0.f;
-    }
-
-    // (as the 16-row kernel's pub, into the cell's tile copy)
-    auto pub = [&](int buf, int sz, unsigned off, float val, unsigned seq) {
-        const float u1 = pdpp<0x39>(val), u2 = pdpp<0x4E>(val), u3 = pdpp<0x93>(val);
-        unsigned vo = off;
-        asm volatile("" : "+v"(vo));
-        __builtin_amdgcn_raw_buffer_store_b128(
-            (u4v){__float_as_uint(val), __float_as_uint(u1), __float_as_uint(u2), __float_as_uint(u3)}, xr, vo,
-            g_slot(buf, sz, seq) + xt, 0);
-        __builtin_amdgcn_raw_buffer_store_b128((u4v){kSentG, kSentG, kSentG, kSentG}, xr, vo,
-                                               g_slot(buf, sz, seq + 1u) + xt, 0);
-    };
-    // partial tile j of a product, column tile `tile`, into P ([tile][v][nt][n][m], swizzled)
-    auto put = [&](int P, int NT, int tile, int j, const v4f& acc) {
-        *reinterpret_cast<v4f*>(lds + P + tile * NT * WT + ((v * NT + j) * 16 + bn) * 16 + wsw(bn, 4 * (l >> 4))) = acc;
-    };
-    // the cell's sum of the 8 waves' partials of tile j, tile row m (fixed order v = 0 .. 7)
-    auto psum = [&](int P, int NT, int j, int m) {
-        float p[8];
-#pragma unroll
-        for (int vv = 0; vv < 8; ++vv)
-            p[vv] = lds[P + tt * NT * WT + ((vv * NT + j) * 16 + cnl) * 16 + wsw(cnl, m)];
-        float acc = 0.f;
-#pragma unroll
-        for (int vv = 0; vv < 8; ++vv) acc += p[vv];
-        return acc;
-    };
-
-    float h1r = 0.f, x1c = 0.f;
-    if (gcell) {  // x1, h1 of step 0 (k_persist_gen_init)
-        const float* st = a.st + (size_t)crow * 2 * GH;
-        x1c = st[cu];
-        h1r = st[GH + cu];
-    }
-    const float vr = gcell ? a.v[cu] : 0.f, vz = gcell ? a.v[GH + cu] : 0.f, vn = gcell ? a.v[2 * GH + cu] : 0.f;
-    const float w0c = gcell ? a.w0[cu] : 0.f;
-    const float* cb = lds + W2_CB;
+    gen_load_weights(a, c, wq);
+    gen_setup_lds(a, c);
+    GenState s = gen_state(a, c);
     const rsrc_t fcr = mk_rsrc(a.fcond);
-    const unsigned o_gn = (unsigned)(crow * kMolNoise + cul) * 4u;  // (MOL draw stream)
-    [[maybe_unused]] float pg = 0.f, pgn = 0.f;
-    [[maybe_unused]] auto mol_draw = [&](int te) {
-        const int tc = te < a.S ? te : a.S - 1;
-        if (cell && cul < kMolNoise) pgn = bld(mk_rsrc(a.gumbel + (size_t)tc * a.B * kMolNoise), o_gn, 0);
-    };
-    [[maybe_unused]] const bool l_ra = cell && cul < a.n_classes, l_rb = cell && 16 + cul < a.n_classes;
-    [[maybe_unused]] const unsigned o_lp =
-        cell && w < 2 && 16 * w + cul < a.n_classes ? g_logit(cnl, 16 * w + cul) : kNoOff;
     // thread i of a wave set forms, for its tile, the P1 cell (row i / 8, unit i % 8) and, BITS, the
     // noise cell (row i / 16, thread i % 16 of the row) of the rows below R
     const int ri_ = tid & 255;
-    const int n1 = kRowsW * tt + (ri_ >> 3), n2 = kRowsW * tt + (ri_ >> 4);
-    const bool p1do = n1 < R, nzdo = MODE == 0 && n2 < R;
-    auto ring_make = [&](int t_noise, int t_p1) {  // (the prologue: both parts at once)
-        if (p1do) ring_p1_make<W2_RI, W2_P1R>(a, lds, w, n1, ri_ & 7, t_p1);
-        if constexpr (MODE == 0)
-            if (nzdo) ring_noise_make<W2_RI, W2_GR>(a, lds, w, ntc, n2, ri_ & 15, t_noise);
-    };
+    const int n1 = kRowsW * c.tt + (ri_ >> 3), n2 = kRowsW * c.tt + (ri_ >> 4);
+    const bool p1do = n1 < c.R, nzdo = MODE == 0 && n2 < c.R;
     __syncthreads();
-    // ring prologue: the noise of step t0 and P1(t0 + 1), read after step t0's first barrier
-    ring_make(a.t0, a.t0 + 1);
+    // ring prologue (both parts at once): the noise of step t0 and P1(t0 + 1), read after step t0's
+    // first barrier
+    if (p1do) ring_p1_make<L>(a, lds, w, n1, ri_ & 7, a.t0 + 1);
+    if constexpr (MODE == 0)
+        if (nzdo) ring_noise_make<L>(a, lds, w, c.ntc, n2, ri_ & 15, a.t0);
     if constexpr (MODE == 1) {
-        mol_draw(a.t0);
-        pg = pgn;
+        gen_mol_draw(a, c, s, a.t0);
+        s.pg = s.pgn;
     }
-    pub(GX_X1, GS_X, o_px, __builtin_canonicalizef(x1c), (unsigned)a.t0 + 1u);
-    pub(GX_H1, GS_X, o_px, __builtin_canonicalizef(h1r), (unsigned)a.t0 + 1u);
+    gen_pub_initial(a, c, s);
     bool fail = false;
     u4v c0[2], c1[2];
     if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[0] = p_now();
     for (int t = a.t0; t < a.t1; ++t) {
         const unsigned seq = (unsigned)t + 1u;
-        float pc = 0.f;
+        const float pc = gen_fc1_cond(a, c, fcr, t);
         [[maybe_unused]] float pn[2] = {0.f, 0.f};
         float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (fcell) pc = bld(fcr, (unsigned)(p_frame(rinfo[cn], t, a.hop) * a.cond_width + a.oF1 + GO * w + cul) * 4u, 0);
-        if constexpr (MODE == 1) mol_draw(t + 1);
+        if constexpr (MODE == 1) gen_mol_draw(a, c, s, t + 1);
         // the thread's ring cells of the next step, first part: the table loads of P1(t + 2) are in
         // flight over the whole step, the Philox words of step t + 1 and the first Gumbel word are
         // formed in the wait for x1; the values go to LDS after the second barrier
         RingP1Taps pt;
         [[maybe_unused]] uint32_t nw0 = 0, nw1 = 0, ng0 = 0;
-        if (p1do) ring_p1_load(a, rinfo[n1], w, ri_ & 7, t + 2, pt);
+        if (p1do) ring_p1_load(a, c.row(n1), w, ri_ & 7, t + 2, pt);
         if constexpr (MODE == 0) {
             if (nzdo) {
-                ring_noise_words(a, rinfo[n2], w, ntc, ri_ & 15, t + 1, nw0, nw1);
+                ring_noise_words(a, c.row(n2), w, c.ntc, ri_ & 15, t + 1, nw0, nw1);
                 ng0 = gumbel_q_of(nw0);
             }
             asm volatile("" : "+v"(ng0), "+v"(nw1));
         }
         // ---- hop 1: x1 of every slot, both tiles -> fc1 -> y1 --------------------------------
-        fail |= !g_poll2<2>(xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid0, bvalid1, c0, c1, a.ctl, wh(1), (unsigned)t);
+        fail |= !g_poll2<2>(c.xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid0, bvalid1, c0, c1, a.ctl, c.wh(1), (unsigned)t);
         {
             v4f e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -928,31 +848,16 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen32(PersistGenRingArg
                 e0 = mfma4(wa, u4c(c0[ks >> 2], ks & 3), e0);
                 e1 = mfma4(wa, u4c(c1[ks >> 2], ks & 3), e1);
             }
-            put(W2P_F1, 1, 0, 0, e0);
-            put(W2P_F1, 1, 1, 0, e1);
+            c.put(L::F1, 1, 0, 0, e0);
+            c.put(L::F1, 1, 1, 0, e1);
         }
-        if (fail) lds[W2_FAIL] = 1.f;
-        gbar();
-        if (lds[W2_FAIL] != 0.f) return;
-        {
-            float y = 0.f;
-            if (fcell) {
-                y = p_add(psum(W2P_F1, 1, 0, cul), pc);
-                y = y > 0.f ? y : 0.f;
-            }
-            pub(GX_Y1, GS_Y, o_py, y, seq);
-            // the tile's noise of step t and P1(t + 1): written before the barrier above (step
-            // t - 1's epilogue, or the prologue), overwritten only after the barrier below
-            if constexpr (MODE == 0) {
-                if (cell) {
-                    pn[0] = lds[W2_GR + cn * kGrW + cul];
-                    if (ntc == 2) pn[1] = lds[W2_GR + cn * kGrW + 16 + cul];
-                }
-            }
-            if (gcell) pp = reinterpret_cast<const float4*>(lds + W2_P1R)[cn * GU + cul];
-        }
+        if (fail) lds[L::FAIL] = 1.f;
+        lds_barrier();
+        if (lds[L::FAIL] != 0.f) return;
+        gen_pub_y1(c, pc, seq);
+        gen_ring_read<MODE>(c, pn, pp);
         // ---- in the wait for y1: h1 of every slot -> W_hh1 h1 ---------------------------------
-        fail |= !g_poll2<2>(xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid0, bvalid1, c0, c1, a.ctl, wh(2), (unsigned)t);
+        fail |= !g_poll2<2>(c.xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid0, bvalid1, c0, c1, a.ctl, c.wh(2), (unsigned)t);
         {
             v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
             v4f b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
@@ -965,13 +870,13 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen32(PersistGenRingArg
                 a1 = mfma4(wb, x0, a1);
                 b1 = mfma4(wb, x1, b1);
             }
-            put(W2P_HH, 2, 0, 0, a0);
-            put(W2P_HH, 2, 0, 1, a1);
-            put(W2P_HH, 2, 1, 0, b0);
-            put(W2P_HH, 2, 1, 1, b1);
+            c.put(L::HH, 2, 0, 0, a0);
+            c.put(L::HH, 2, 0, 1, a1);
+            c.put(L::HH, 2, 1, 0, b0);
+            c.put(L::HH, 2, 1, 1, b1);
         }
         // ---- hop 2: y1 of every slot -> fc3 -> the slot's candidate of every row ------------
-        fail |= !g_poll2<1>(xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid0, bvalid1, c0, c1, a.ctl, wh(3), (unsigned)t);
+        fail |= !g_poll2<1>(c.xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid0, bvalid1, c0, c1, a.ctl, c.wh(3), (unsigned)t);
         {
             v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
             v4f b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
@@ -980,325 +885,166 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen32(PersistGenRingArg
                 const float x0 = u4c(c0[0], ks), x1 = u4c(c1[0], ks);
                 a0 = mfma4(f4c(wq[6], ks), x0, a0);
                 b0 = mfma4(f4c(wq[6], ks), x1, b0);
-                if (ntc == 2) {
+                if (c.ntc == 2) {
                     a1 = mfma4(f4c(wq[7], ks), x0, a1);
                     b1 = mfma4(f4c(wq[7], ks), x1, b1);
                 }
             }
-            put(W2P_F3, 2, 0, 0, a0);
-            put(W2P_F3, 2, 1, 0, b0);
-            if (ntc == 2) {
-                put(W2P_F3, 2, 0, 1, a1);
-                put(W2P_F3, 2, 1, 1, b1);
+            c.put(L::F3, 2, 0, 0, a0);
+            c.put(L::F3, 2, 1, 0, b0);
+            if (c.ntc == 2) {
+                c.put(L::F3, 2, 0, 1, a1);
+                c.put(L::F3, 2, 1, 1, b1);
             }
         }
-        if (fail) lds[W2_FAIL] = 1.f;
-        gbar();
+        if (fail) lds[L::FAIL] = 1.f;
+        lds_barrier();
         {
-            [[maybe_unused]] const unsigned want = key_tag(seq);
-            float g1r = 0.f, g1z = 0.f, g1n = 0.f;
-            if constexpr (MODE == 0) {
-                uint32_t kh = 0, kl = 0;
-                if (cell) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        if (j >= ntc) break;
-                        const int c = a.cpw * w + 16 * j + cul;
-                        const float lg = p_add(psum(W2P_F3, 2, j, cul), cb[32 + 16 * j + cul]);
-                        p_dbg_logit<DBG>(a.dbg, t, crow, c, a.B, a.n_classes, lg);
-                        const CandKey k = cand_key(lg, __float_as_uint(pn[j]), c);
-                        kmax_take(kh, kl, k.hi, k.lo);
-                    }
-                }
-                row16_kmax(kh, kl);
-                unsigned vo = cell && cul == 0 ? g_cand(cnl, w) : kNoOff;
-                asm volatile("" : "+v"(vo));
-                __builtin_amdgcn_raw_buffer_store_b64((u2v){kh, kl | want}, xr, vo, GX_D * 4 + xt, 0);
-            } else {
-                float lg = 0.f;
-                if (o_lp != kNoOff) {
-                    lg = p_add(psum(W2P_F3, 2, 0, cul), cb[32 + cul]);
-                    p_dbg_logit<DBG>(a.dbg, t, crow, 16 * w + cul, a.B, a.n_classes, lg);
-                }
-                unsigned vo = o_lp;
-                asm volatile("" : "+v"(vo));
-                __builtin_amdgcn_raw_buffer_store_b64((u2v){__float_as_uint(lg), seq}, xr, vo, GX_D * 4 + xt, 0);
-            }
-            if (gcell) {  // gh1 = W_hh1 h1 + b_hh1 of the cell's unit
-                g1r = p_add(psum(W2P_HH, 2, 0, cul), cb[cul]);
-                g1z = p_add(psum(W2P_HH, 2, 0, 8 + cul), cb[8 + cul]);
-                g1n = p_add(psum(W2P_HH, 2, 1, cul), cb[16 + cul]);
-            }
+            float g1r, g1z, g1n;
+            gen_pub_fc3<MODE, DBG>(a, c, s, pn, t, seq);
+            gen_gh1(c, g1r, g1z, g1n);
             // second part, while the candidates travel: the tile's noise of step t + 1 and P1(t + 2)
             if constexpr (MODE == 0) {
                 if (nzdo) {
-                    float* dst = lds + W2_GR + n2 * kGrW + (ntc == 2 ? 2 * (ri_ & 15) : (ri_ & 15));
+                    float* dst = ring_noise_dst<L>(lds, c.ntc, n2, ri_ & 15);
                     dst[0] = __uint_as_float(ng0);
-                    if (ntc == 2) dst[1] = __uint_as_float(gumbel_q_of(nw1));
+                    if (c.ntc == 2) dst[1] = __uint_as_float(gumbel_q_of(nw1));
                 }
             }
-            if (p1do) reinterpret_cast<float4*>(lds + W2_P1R)[n1 * GU + (ri_ & 7)] = ring_p1_finish(pt);
-            // ---- hop 3: sample of step t ------------------------------------------------------
-            float x;
-            if constexpr (MODE == 0) {
-                u4v q = {0u, want, 0u, want};
-                const unsigned t0s = p_now();
-                unsigned nsp = 0;
-                while (true) {
-                    if (cell) {
-                        unsigned vo = g_cand(cnl, 2 * cul);
-                        asm volatile("" : "+v"(vo));
-                        q = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, GX_D * 4 + xt, kCpNT);
-                    }
-                    if (__all(((q.y & kKeyTagMask) == want) & ((q.w & kKeyTagMask) == want))) break;
-                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
-                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
-                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(4) | ((unsigned)v << 19)) == 0u) {
-                            a.ctl[PC_WHERE + 1] = 1u;
-                            a.ctl[PC_WHERE + 2] = (unsigned)t;
-                        }
-                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
-                        fail = true;
-                        break;
-                    }
-                }
-                uint32_t bh = cell ? q.x : 0u, bl = cell ? q.y : 0u;
-                kmax_take(bh, bl, cell ? q.z : 0u, cell ? q.w : 0u);
-                row16_kmax(bh, bl);
-                const int bi = key_cls(bl);
-                {
-#pragma clang fp contract(off)
-                    x = (2.0f * (float)bi) / (float)(a.n_classes - 1) - 1.0f;
-                }
-                if (w == 0 && cell && cul == 0) {
-                    int nn = cn;
-                    asm volatile("" : "+v"(nn));
-                    const unsigned ro = (unsigned)((g0 + kPG * nn) * a.ld);
-                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u,
-                                                          (unsigned)t * 2u, 0);
-                    bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
-                }
-            } else {
-                unsigned va = l_ra ? g_logit(cnl, cul) : kNoOff;
-                unsigned vb = l_rb ? g_logit(cnl, 16 + cul) : kNoOff;
-                asm volatile("" : "+v"(va), "+v"(vb));
-                u2v qa, qb;
-                const unsigned t0s = p_now();
-                unsigned nsp = 0;
-                while (true) {
-                    qa = __builtin_amdgcn_raw_buffer_load_b64(xr, va, GX_D * 4 + xt, kCpNT);
-                    qb = __builtin_amdgcn_raw_buffer_load_b64(xr, vb, GX_D * 4 + xt, kCpNT);
-                    if (__all((!l_ra | (qa.y == seq)) & (!l_rb | (qb.y == seq)))) break;
-                    if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
-                        if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
-                            atomicCAS(a.ctl + PC_WHERE, 0u, wh(5) | ((unsigned)v << 19)) == 0u) {
-                            a.ctl[PC_WHERE + 1] = 1u;
-                            a.ctl[PC_WHERE + 2] = (unsigned)t;
-                        }
-                        if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
-                        fail = true;
-                        break;
-                    }
-                }
-                const float la = __uint_as_float(qa.x);
-                [[maybe_unused]] const float lb = __uint_as_float(qb.x);
-                const int base = l & 48;  // lane 0 of this lane's row
-                if constexpr (MODE == 2) {
-                    double gv = 0.0;
-                    if (cell && cul < 2) {
-                        const RowInfo& ri = rinfo[cn];
-                        gv = gamma_mt((double)expf(la), (uint32_t)cul, (uint32_t)t, (uint32_t)ri.fold, ri.stream,
-                                      a.k0, a.k1);
-                    }
-                    const double gy = __shfl(gv, base + 1);
-                    float xv = 0.f;
-                    {
-#pragma clang fp contract(off)
-                        const float sb = (float)(gv / (gv + gy));
-                        xv = 2.0f * sb - 1.0f;
-                    }
-                    x = __shfl(xv, base);
-                } else {
-                    float bv;
-                    {
-#pragma clang fp contract(off)
-                        bv = cul < 10 ? la - pg : -INFINITY;
-                    }
-                    int bi = cul < 10 ? cul : 0x7fffffff;
-                    row16_argmax(bv, bi);
-                    bi = bi < 10 ? bi : 0;
-                    const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
-                    const float mean = bi < 6 ? m0 : m1;
-                    float ls = __shfl(lb, base + 4 + bi);
-                    const float lu = __shfl(pg, base + 10);
-                    {
-#pragma clang fp contract(off)
-                        const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
-                        ls = ls < lsmin ? lsmin : ls;
-                        x = mean + expf(ls) * lu;
-                        x = x < -1.f ? -1.f : x;
-                        x = x > 1.f ? 1.f : x;
-                    }
-                    pg = pgn;
-                }
-                if (w == 0 && cell && cul == 0) {
-                    int nn = cn;
-                    asm volatile("" : "+v"(nn));
-                    bst(x, mk_rsrc(a.samples), (unsigned)((g0 + kPG * nn) * a.ld) * 4u, (unsigned)t * 4u);
-                }
-            }
-            if (fail) lds[W2_FAIL] = 1.f;  // seen by every wave at the next step's check
-            // ---- GRU1 of step t + 1 for the slot's units -> x1, h1 ---------------------------
-            float x1 = 0.f;
-            if (gcell) {
-                h1r = p_gru(fmaf(vr, x, pp.x), fmaf(vz, x, pp.y), fmaf(vn, x, pp.z), g1r, g1z, g1n, h1r);
-                x1 = p_add(fmaf(w0c, x, pp.w), h1r);
-            }
-            pub(GX_X1, GS_X, o_px, x1, seq + 1u);
-            pub(GX_H1, GS_X, o_px, h1r, seq + 1u);
+            if (p1do) reinterpret_cast<float4*>(lds + L::P1R)[n1 * GU + (ri_ & 7)] = ring_p1_finish(pt);
+            const float x = gen_sample<MODE>(a, c, s, t, seq, fail);
+            if (fail) lds[L::FAIL] = 1.f;  // seen by every wave at the next step's check
+            gen_gru1_pub(c, s, x, pp, g1r, g1z, g1n, seq);
         }
-        if (w == 0 && tid == 0) {
-            if (g == 0) p_progress(a.progress, a.prog_base, t);
-            if (p_abort(a.ctl, a.progress, t)) lds[W2_FAIL] = 1.f;  // seen at the next step's check
-        }
+        gen_step_end(a, c, t);
     }
     if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
 }
 
 // launch-side helpers --------------------------------------------------------------------
+namespace {
 // at least 96 KB so that no CU can take two workgroups of this (register-light) kernel: every
 // group must span 32 CUs
-size_t persist_wide_gen_lds_bytes() {
-    const size_t need = (size_t)WL_TOTAL_RING * sizeof(float);  // (the stream instances use WL_TOTAL of it)
+constexpr size_t gen_lds_bytes(int floats) {
+    const size_t need = (size_t)floats * sizeof(float);
     return need > 96 * 1024 ? need : 96 * 1024;
 }
-size_t persist_wide_gen_xbuf_floats() { return (size_t)kPG * GX_GROUP; }
-size_t persist_wide_gen_wreg_floats() { return (size_t)kPM * 8 * kWgq * 64 * 4; }
-// before every launch: the vector slots to the sentinel, the candidate area (step tags) to 0
-__global__ __launch_bounds__(256) void k_wide_gen_xbuf_reset(uint4* x) {
+// before every launch: the vector slots to the sentinel, the candidate / logit areas (step tags)
+// to 0, over n16 16-byte units (every tile copy is GX_GROUP floats)
+__global__ __launch_bounds__(256) void k_wide_gen_xbuf_reset(uint4* x, size_t n16) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)kPG * GX_GROUP / 4) return;
+    if (i >= n16) return;
     const unsigned f = (unsigned)((i * 4) % GX_GROUP);
-    x[i] = f >= (unsigned)GX_D ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(kSentG, kSentG, kSentG, kSentG);
+    x[i] = f >= (unsigned)GX_D ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(kSent, kSent, kSent, kSent);
 }
-hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s) {
-    const unsigned n = (unsigned)((size_t)kPG * GX_GROUP / 4);
-    k_wide_gen_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf));
+hipError_t gen_reset_xbuf(float* xbuf, size_t floats, hipStream_t s) {
+    const unsigned n = (unsigned)(floats / 4);
+    k_wide_gen_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf), floats / 4);
     return hipGetLastError();
 }
-namespace {
-template <bool RING, bool DBG>
-const void* wide_gen_fn(int mode) {
-    return mode == 2 ? (const void*)k_persist_wide_gen<2, RING, DBG>
-         : mode == 1 ? (const void*)k_persist_wide_gen<1, RING, DBG>
-         : mode == 0 ? (const void*)k_persist_wide_gen<0, RING, DBG> : nullptr;
+
+// The three kernel families, instance <MODE, DBG> of each, and the one (mode x DBG) dispatch:
+// f(instance) for the family's instance of (mode 0 .. 2, dbg), the kernel as decltype(k)::value
+struct Gen16Stream {
+    using Args = PersistGenArgs;
+    template <int MODE, bool DBG>
+    static constexpr auto k = k_persist_wide_gen<MODE, false, DBG>;
+};
+struct Gen16Ring {
+    using Args = PersistGenRingArgs;
+    template <int MODE, bool DBG>
+    static constexpr auto k = k_persist_wide_gen<MODE, true, DBG>;
+};
+struct Gen32Ring {
+    using Args = PersistGenRingArgs;
+    template <int MODE, bool DBG>
+    static constexpr auto k = k_persist_wide_gen32<MODE, DBG>;
+};
+template <class Fam, int MODE, bool DBG>
+using GenInst = std::integral_constant<void (*)(typename Fam::Args), Fam::template k<MODE, DBG>>;
+template <class Fam, class F>
+auto gen_dispatch(int mode, bool dbg, F&& f) {
+    if (mode == 2) return dbg ? f(GenInst<Fam, 2, true>{}) : f(GenInst<Fam, 2, false>{});
+    if (mode == 1) return dbg ? f(GenInst<Fam, 1, true>{}) : f(GenInst<Fam, 1, false>{});
+    return dbg ? f(GenInst<Fam, 0, true>{}) : f(GenInst<Fam, 0, false>{});
 }
-const void* wide_gen_fn(int mode, bool ring, bool dbg) {
-    return ring ? (dbg ? wide_gen_fn<true, true>(mode) : wide_gen_fn<true, false>(mode))
-                : (dbg ? wide_gen_fn<false, true>(mode) : wide_gen_fn<false, false>(mode));
+// scratch bytes of one instance (-1: no such mode, or the query failed)
+template <class Fam>
+int gen_scratch_of(int mode, bool dbg) {
+    if (mode < 0 || mode > 2) return -1;
+    return gen_dispatch<Fam>(mode, dbg, [](auto k) {
+        hipFuncAttributes fa;
+        const void* fn = reinterpret_cast<const void*>(decltype(k)::value);
+        return hipFuncGetAttributes(&fa, fn) == hipSuccess ? (int)fa.localSizeBytes : -1;
+    });
+}
+// the larger scratch of a mode's production and DBG instance: a constant of the build, read from
+// the code objects once per mode
+template <class Fam>
+int gen_scratch_max(int mode) {
+    if (mode < 0 || mode > 2) return -1;
+    static int cached[3] = {-2, -2, -2};  // -2: not read yet
+    if (cached[mode] == -2) {
+        const int p = gen_scratch_of<Fam>(mode, false), d = gen_scratch_of<Fam>(mode, true);
+        if (p < 0 || d < 0) return -1;
+        cached[mode] = p > d ? p : d;
+    }
+    return cached[mode];
+}
+// whole launches (t0 = 0: x1, h1 of k_persist_gen_init) of BITS rows with 512 or 1024 classes
+// (1 or 2 fc3 tiles of 16 per slot), of MOL rows (30 logits; the draws come from the k_mol_noise
+// stream) or of BETA rows (2): one tile in slots 0 and 1; no rotated or time-sliced instance
+bool gen_args_ok(const PersistGenArgs& a, int max_rows) {
+    if (a.rb < 0 || a.nr < 1 || a.nr > max_rows || a.rb + kPG * a.nr > a.B || a.t0 != 0 || a.t1 != a.S ||
+        a.vmap != nullptr || a.wwide == nullptr)
+        return false;
+    if (a.mode == 1) return a.cpw == 16 && a.n_classes == 30 && a.gumbel != nullptr;
+    if (a.mode == 2) return a.cpw == 16 && a.n_classes == 2;
+    return a.mode == 0 && (a.n_classes == 512 || a.n_classes == 1024) && a.cpw * kPM == a.n_classes;
+}
+// ring launches form P1 from the per-frame tables and read no stream, so the tables must all be there
+bool gen_ring_args_ok(const PersistGenRingArgs& a) {
+    return a.p1q && a.p1a && a.p1taps && a.hop > 0 && a.p1split >= 0 && a.mode >= 0 && a.mode <= 2;
+}
+template <class Fam>
+hipError_t gen_launch(const typename Fam::Args& a, int max_rows, size_t lds, hipStream_t s) {
+    if (!gen_args_ok(a, max_rows)) return hipErrorInvalidValue;
+    return gen_dispatch<Fam>(a.mode, a.dbg.out != nullptr,
+                             [&](auto k) { return persist_launch<decltype(k)::value>(lds, a, s); });
 }
 }  // namespace
+
+size_t persist_wide_gen_lds_bytes() { return gen_lds_bytes(GenLds<1>::TOTAL_RING); }  // (stream instances use TOTAL of it)
+size_t persist_wide_gen_xbuf_floats() { return (size_t)kPG * GX_GROUP; }
+size_t persist_wide_gen_wreg_floats() { return (size_t)kPM * 8 * kWgq * 64 * 4; }
+hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s) {
+    return gen_reset_xbuf(xbuf, persist_wide_gen_xbuf_floats(), s);
+}
 // scratch bytes of the mode's stream instances (0 BITS, 1 MOL, 2 BETA): the larger of production
 // and DBG (BITS: the production instance, as the planner has always read it)
 int persist_wide_gen_scratch(int mode) {
-    hipFuncAttributes fa, fd;
-    const void* f = wide_gen_fn(mode, false, false);
-    const void* d = wide_gen_fn(mode, false, true);
-    if (!f || hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
-    if (mode == 0) return (int)fa.localSizeBytes;
-    if (hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
-    return (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
+    return mode == 0 ? gen_scratch_of<Gen16Stream>(0, false) : gen_scratch_max<Gen16Stream>(mode);
 }
-// ... and of its ring instances (the larger of production and DBG): a ring launch needs 0. A
-// constant of the build, read from the code objects once per mode
-int persist_wide_gen_ring_scratch(int mode) {
-    if (mode < 0 || mode > 2) return -1;
-    static int cached[3] = {-2, -2, -2};  // -2: not read yet
-    if (cached[mode] == -2) {
-        hipFuncAttributes fa, fd;
-        const void* f = wide_gen_fn(mode, true, false);
-        const void* d = wide_gen_fn(mode, true, true);
-        if (hipFuncGetAttributes(&fa, f) != hipSuccess || hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
-        cached[mode] = (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
-    }
-    return cached[mode];
-}
-namespace {
-// the checks common to both forms, then the head's instance K<MODE, DBG>
-template <bool RING, typename Args>
-hipError_t wide_gen_launch(const Args& a, hipStream_t s) {
-    // whole launches (t0 = 0: x1, h1 of k_persist_gen_init) of BITS rows with 512 or 1024 classes
-    // (1 or 2 fc3 tiles of 16 per slot), of MOL rows (30 logits) or of BETA rows (2): one tile in
-    // slots 0 and 1; no rotated or time-sliced instance
-    if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || a.t0 != 0 || a.t1 != a.S ||
-        a.vmap != nullptr || a.wwide == nullptr)
-        return hipErrorInvalidValue;
-    const size_t lb = persist_wide_gen_lds_bytes();
-    if (a.mode == 1) {  // (the draws come from the k_mol_noise stream)
-        if (a.cpw != 16 || a.n_classes != 30 || a.gumbel == nullptr) return hipErrorInvalidValue;
-        return a.dbg.out ? persist_launch<k_persist_wide_gen<1, RING, true>>(lb, a, s)
-                         : persist_launch<k_persist_wide_gen<1, RING, false>>(lb, a, s);
-    }
-    if (a.mode == 2) {
-        if (a.cpw != 16 || a.n_classes != 2) return hipErrorInvalidValue;
-        return a.dbg.out ? persist_launch<k_persist_wide_gen<2, RING, true>>(lb, a, s)
-                         : persist_launch<k_persist_wide_gen<2, RING, false>>(lb, a, s);
-    }
-    if (a.mode != 0 || (a.n_classes != 512 && a.n_classes != 1024) || a.cpw * kPM != a.n_classes)
-        return hipErrorInvalidValue;
-    return a.dbg.out ? persist_launch<k_persist_wide_gen<0, RING, true>>(lb, a, s)
-                     : persist_launch<k_persist_wide_gen<0, RING, false>>(lb, a, s);
-}
-}  // namespace
+// ... and of its ring instances (the larger of production and DBG): a ring launch needs 0
+int persist_wide_gen_ring_scratch(int mode) { return gen_scratch_max<Gen16Ring>(mode); }
 hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s) {
-    return wide_gen_launch<false>(a, s);
+    return gen_launch<Gen16Stream>(a, kPWideRows, persist_wide_gen_lds_bytes(), s);
 }
-// ring launch: P1 is formed from the per-frame tables and no stream is read, so the tables must
-// all be there; the instances must run without scratch
+// ring launch: the instances must run without scratch
 hipError_t launch_persist_wide_gen_ring(const PersistGenRingArgs& a, hipStream_t s) {
-    if (!a.p1q || !a.p1a || !a.p1taps || a.hop <= 0 || a.p1split < 0 || a.mode < 0 || a.mode > 2 ||
-        persist_wide_gen_ring_scratch(a.mode) != 0)
-        return hipErrorInvalidValue;
-    return wide_gen_launch<true>(a, s);
+    if (!gen_ring_args_ok(a) || persist_wide_gen_ring_scratch(a.mode) != 0) return hipErrorInvalidValue;
+    return gen_launch<Gen16Ring>(a, kPWideRows, persist_wide_gen_lds_bytes(), s);
 }
 
 // ---- 32-row ring instances: launch side ---------------------------------------------------
-size_t persist_wide_gen32_lds_bytes() {
-    const size_t need = (size_t)W2_TOTAL * sizeof(float);
-    return need > 96 * 1024 ? need : 96 * 1024;  // (one workgroup per CU, as above)
-}
+size_t persist_wide_gen32_lds_bytes() { return gen_lds_bytes(GenLds<2>::TOTAL_RING); }
 size_t persist_wide_gen32_xbuf_floats() { return (size_t)kPG * GX_GROUP32; }
-// before every 32-row launch: both tile copies of every group, vector slots to the sentinel, the
-// candidate / logit areas to 0
-__global__ __launch_bounds__(256) void k_wide_gen32_xbuf_reset(uint4* x) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)kPG * GX_GROUP32 / 4) return;
-    const unsigned f = (unsigned)((i * 4) % GX_GROUP);  // (a tile copy is GX_GROUP floats)
-    x[i] = f >= (unsigned)GX_D ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(kSentG, kSentG, kSentG, kSentG);
-}
+// (both tile copies of every group)
 hipError_t persist_wide_gen32_reset_xbuf(float* xbuf, hipStream_t s) {
-    const unsigned n = (unsigned)((size_t)kPG * GX_GROUP32 / 4);
-    k_wide_gen32_xbuf_reset<<<(n + 255) / 256, 256, 0, s>>>(reinterpret_cast<uint4*>(xbuf));
-    return hipGetLastError();
+    return gen_reset_xbuf(xbuf, persist_wide_gen32_xbuf_floats(), s);
 }
-// scratch bytes of the mode's 32-row instances (the larger of production and DBG), read from the
-// code objects once per mode; -1: no such instance
-int persist_wide_gen32_scratch(int mode) {
-    if (mode < 0 || mode > 2) return -1;
-    static int cached[3] = {-2, -2, -2};  // -2: not read yet
-    if (cached[mode] == -2) {
-        hipFuncAttributes fa, fd;
-        const void* f = mode == 2 ? (const void*)k_persist_wide_gen32<2, false>
-                      : mode == 1 ? (const void*)k_persist_wide_gen32<1, false>
-                                  : (const void*)k_persist_wide_gen32<0, false>;
-        const void* d = mode == 2 ? (const void*)k_persist_wide_gen32<2, true>
-                      : mode == 1 ? (const void*)k_persist_wide_gen32<1, true>
-                                  : (const void*)k_persist_wide_gen32<0, true>;
-        if (hipFuncGetAttributes(&fa, f) != hipSuccess || hipFuncGetAttributes(&fd, d) != hipSuccess) return -1;
-        cached[mode] = (int)(fa.localSizeBytes > fd.localSizeBytes ? fa.localSizeBytes : fd.localSizeBytes);
-    }
-    return cached[mode];
-}
+// scratch bytes of the mode's 32-row instances (the larger of production and DBG); -1: no such instance
+int persist_wide_gen32_scratch(int mode) { return gen_scratch_max<Gen32Ring>(mode); }
 // the scratch a 32-row launch of the mode may carry: none; Beta at most the 16-byte frame its
 // other instances are accepted with
 bool persist_wide_gen32_usable(int mode) {
@@ -1307,26 +1053,8 @@ bool persist_wide_gen32_usable(int mode) {
 }
 // whole launches of up to 32 rows per group (t0 = 0), heads as launch_persist_wide_gen_ring
 hipError_t launch_persist_wide_gen32_ring(const PersistGenRingArgs& a, hipStream_t s) {
-    if (!a.p1q || !a.p1a || !a.p1taps || a.hop <= 0 || a.p1split < 0 || a.mode < 0 || a.mode > 2 ||
-        !persist_wide_gen32_usable(a.mode))
-        return hipErrorInvalidValue;
-    if (a.rb < 0 || a.nr < 1 || a.nr > kRows32 || a.rb + kPG * a.nr > a.B || a.t0 != 0 || a.t1 != a.S ||
-        a.vmap != nullptr || a.wwide == nullptr)
-        return hipErrorInvalidValue;
-    const size_t lb = persist_wide_gen32_lds_bytes();
-    if (a.mode == 1) {  // (the draws come from the k_mol_noise stream)
-        if (a.cpw != 16 || a.n_classes != 30 || a.gumbel == nullptr) return hipErrorInvalidValue;
-        return a.dbg.out ? persist_launch<k_persist_wide_gen32<1, true>>(lb, a, s)
-                         : persist_launch<k_persist_wide_gen32<1, false>>(lb, a, s);
-    }
-    if (a.mode == 2) {
-        if (a.cpw != 16 || a.n_classes != 2) return hipErrorInvalidValue;
-        return a.dbg.out ? persist_launch<k_persist_wide_gen32<2, true>>(lb, a, s)
-                         : persist_launch<k_persist_wide_gen32<2, false>>(lb, a, s);
-    }
-    if ((a.n_classes != 512 && a.n_classes != 1024) || a.cpw * kPM != a.n_classes) return hipErrorInvalidValue;
-    return a.dbg.out ? persist_launch<k_persist_wide_gen32<0, true>>(lb, a, s)
-                     : persist_launch<k_persist_wide_gen32<0, false>>(lb, a, s);
+    if (!gen_ring_args_ok(a) || !persist_wide_gen32_usable(a.mode)) return hipErrorInvalidValue;
+    return gen_launch<Gen32Ring>(a, kRows32, persist_wide_gen32_lds_bytes(), s);
 }
 
 // Exhaustive host check of the exchange layout (as wide_rr_layout_check): for every row count,

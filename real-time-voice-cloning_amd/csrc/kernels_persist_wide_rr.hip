@@ -31,7 +31,7 @@
 // kernels_persist_wide.hip) -- consumer and producer halves alternate, so every
 // consumer has read a later publication of each producer wave before it polls the reset slot.
 #include "wrnn_kernels.h"
-#include "persist_common.h"
+#include "persist_wide_common.h"
 #include "philox.h"
 
 #include <vector>
@@ -39,12 +39,9 @@
 namespace wrnn {
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int RH = kRH;        // 256
 constexpr int kHalf = 16;      // slots per half
 constexpr int kRowsW = 16;     // rows per group (MFMA N)
-constexpr unsigned kSentR = 0x7fbadbadu;  // a signalling NaN: no arithmetic result is ever this
-constexpr unsigned kNoOff = 0x80000000u;  // lanes without a packet: outside every buffer
 
 // ---- exchange area per group (floats) ---------------------------------------------------
 // one vector per step and parity slot: [e 8][p 2][lane 64] packets of 4 floats; packet p of
@@ -106,23 +103,11 @@ static_assert(QL_CB + 224 <= QL_VM && QL_VM + 2 * kRowsW <= QL_P, "small LDS arr
 
 constexpr int kWq = 30;  // float4 weight registers per lane: 15 tiles x 8 k-steps
 
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float f4c(const float4& q, int i) {
-    return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w;
-}
+// (mfma4, f4c, the partial tiles' swizzle wsw, packet_ready and lds_barrier: persist_wide_common.h)
 __device__ __forceinline__ float bop2(const u4v (&cc)[2], int ks) {
     const u4v& q = cc[ks >> 2];
     return __uint_as_float((ks & 3) == 0 ? q.x : (ks & 3) == 1 ? q.y : (ks & 3) == 2 ? q.z : q.w);
 }
-// conflict-free partial tiles: XOR swizzle of the 16-byte column slots by row (as the
-// fatchord wide kernel, kernels_persist_wide.hip wsw)
-__device__ __forceinline__ int wsw(int n, int o) { return ((((o >> 2) ^ (n >> 1)) & 3) << 2) | (o & 3); }
-__device__ __forceinline__ bool q_ready(const u4v& q) {
-    return (q.x != kSentR) & (q.y != kSentR) & (q.z != kSentR) & (q.w != kSentR);
-}
-__device__ __forceinline__ void qbar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // One poll round of a hop: the lane's 2 B-operand packets and (cell lanes) the 4-byte value of
 // its own cell (own == kNoOff: none). Lanes without a packet load from kNoOff (reads 0).
@@ -143,8 +128,11 @@ __device__ __forceinline__ bool q_poll(rsrc_t xr, unsigned voff, unsigned so, bo
     unsigned nsp = 0;
     while (true) {
         q_issue(xr, voff, so, valid, own, cc, ov);
-        if (__all((int)q_ready(cc[0]) & (int)q_ready(cc[1]) & (int)(ov != kSentR))) return true;
+        if (__all((int)packet_ready(cc[0]) & (int)packet_ready(cc[1]) & (int)(ov != kSent))) return true;
         if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
+            // (spin_give_up written out in the per-lane form: the BITS instances sit at 255 VGPRs,
+            // and with the scalar form at this poll's many sites the register allocation of the
+            // two BITS DBG instances changes -- their scratch, tools/isa_check.py resources_of)
             if ((threadIdx.x & 63) == 0 && !ld_sc1_u(ctl + PC_ERR) &&
                 atomicCAS(ctl + PC_WHERE, 0u, where | ((threadIdx.x >> 6) << 19)) == 0u) {
                 ctl[PC_WHERE + 1] = 1u;
@@ -236,7 +224,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
         __builtin_amdgcn_raw_buffer_store_b128(
             (u4v){__float_as_uint(val), __float_as_uint(u1), __float_as_uint(u2), __float_as_uint(u3)}, xr, vo,
             q_slot(hb, seq), 0);
-        __builtin_amdgcn_raw_buffer_store_b128((u4v){kSentR, kSentR, kSentR, kSentR}, xr, vo,
+        __builtin_amdgcn_raw_buffer_store_b128((u4v){kSent, kSent, kSent, kSent}, xr, vo,
                                                q_slot(hb, seq + 1u), 0);
     };
     // NT-tile product over a hop's packets into the partial tiles at P (tiles T0 ..)
@@ -391,7 +379,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             const float x1v = __uint_as_float(ov);
             prod(I3(), 0, cc, PA_G2);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             RS(2);
             if (lds[QL_FAIL] != 0.f) return;
             {
@@ -422,7 +410,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             const float x3v = __uint_as_float(ov);
             prod(I3(), 6, cc, PA_G4);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             {
                 float x4 = 0.f;
                 if (cell) {
@@ -456,7 +444,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             RS(9);
             prod(I1(), 12, cc, PA_F2);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             {
                 float y = 0.f;
                 if (cell) {
@@ -480,7 +468,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             RS(11);
             prod(I1(), 13, cc, PA_F4);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             {
                 float y = 0.f;
                 if (cell) {
@@ -614,7 +602,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             if constexpr (MOL) mol_draw(t + 1);
             prod(I3(), 3, cc, PB_G3);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             if (lds[QL_FAIL] != 0.f) return;
             {
                 float x3 = 0.f;
@@ -649,7 +637,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             RS(6);
             prod(I1(), 9, cc, PB_F1);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             {
                 float y = 0.f;
                 if (cell) {
@@ -672,7 +660,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             RS(8);
             prod(I1(), 10, cc, PB_F3);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             {
                 float y = 0.f;
                 if (cell) {
@@ -695,7 +683,7 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
             else
                 prod(std::integral_constant<int, 2>(), 11, cc, PB_F5);
             if (fail) lds[QL_FAIL] = 1.f;
-            qbar();
+            lds_barrier();
             RS(11);
             if (v < 4) {
                 [[maybe_unused]] const unsigned want = key_tag(seq);
@@ -743,50 +731,13 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
                     // lane (row cn, cul) polls logits cul and 16 + cul of its row (tag: the whole
                     // seq); a lane without a logit loads from kNoOff (reads 0, not waited for)
                     const bool ra = cell && cul < a.n_classes, rb = cell && 16 + cul < a.n_classes;
-                    unsigned va = ra ? q_logit(cn, cul) : kNoOff;
-                    unsigned vb = rb ? q_logit(cn, 16 + cul) : kNoOff;
-                    asm volatile("" : "+v"(va), "+v"(vb));
                     u2v qa, qb;
-                    const unsigned t0s = p_now();
-                    unsigned nsp = 0;
-                    while (true) {
-                        qa = __builtin_amdgcn_raw_buffer_load_b64(xr, va, QX_L * 4, kCpNT);
-                        qb = __builtin_amdgcn_raw_buffer_load_b64(xr, vb, QX_L * 4, kCpNT);
-                        if (__all((!ra | (qa.y == seq)) & (!rb | (qb.y == seq)))) break;
-                        if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
-                            if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
-                                atomicCAS(a.ctl + PC_WHERE, 0u, wh(13) | ((unsigned)v << 19)) == 0u)
-                                a.ctl[PC_WHERE + 2] = (unsigned)t;
-                            if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
-                            fail = true;
-                            break;
-                        }
-                    }
+                    fail |= !poll_logit_pairs(xr, ra ? q_logit(cn, cul) : kNoOff, rb ? q_logit(cn, 16 + cul) : kNoOff,
+                                              QX_L * 4, ra, rb, seq, a.ctl, wh(13), (unsigned)t, false, qa, qb);
                     // the sample: k_persist_rr<MOL>'s operations in its order (kernels_persist_rr.hip,
                     // "MOL:")
                     const float la = __uint_as_float(qa.x), lb = __uint_as_float(qb.x);
-                    float bv;
-                    {
-#pragma clang fp contract(off)
-                        bv = cul < 10 ? la - pg : -INFINITY;
-                    }
-                    int bi = cul < 10 ? cul : 0x7fffffff;
-                    row16_argmax(bv, bi);  // first max over k < 10; every lane of the row gets it
-                    bi = bi < 10 ? bi : 0;
-                    const int base = l & 48;  // lane 0 of this lane's row
-                    // l[10 + bi]: the first value of lane 10 + bi, or the second of lane bi - 6
-                    const float m0 = __shfl(la, base + ((10 + bi) & 15)), m1 = __shfl(lb, base + ((10 + bi) & 15));
-                    const float mean = bi < 6 ? m0 : m1;
-                    float ls = __shfl(lb, base + 4 + bi);  // l[20 + bi]: the second value of lane 4 + bi
-                    const float lu = __shfl(pg, base + 10);
-                    {
-#pragma clang fp contract(off)
-                        const float lsmin = -32.23619130191664f;  // float(np.log(1e-14))
-                        ls = ls < lsmin ? lsmin : ls;
-                        x = mean + expf(ls) * lu;
-                        x = x < -1.f ? -1.f : x;
-                        x = x > 1.f ? 1.f : x;
-                    }
+                    x = mol_sample_row16(la, lb, pg, cul, l);
                     pg = pgn;
                     if (s == 0 && cell && cul == 0) {
                         int nn = cn;
@@ -799,34 +750,15 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_rr(PersistRRArgs a) {
                         bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
                     }
                 } else {
-                    u4v q = {0u, want, 0u, want};
-                    const unsigned t0s = p_now();
-                    unsigned nsp = 0;
+                    u4v q;
                     const bool pl = cell && cul < 8;
-                    while (true) {
-                        if (pl) {
-                            unsigned vo = q_cand(cn, 2 * cul);
-                            asm volatile("" : "+v"(vo));
-                            q = __builtin_amdgcn_raw_buffer_load_b128(xr, vo, QX_D * 4, kCpNT);
-                        }
-                        if (__all(((q.y & kKeyTagMask) == want) & ((q.w & kKeyTagMask) == want))) break;
-                        if ((++nsp & 63) == 0 && (ld_sc1_u(a.ctl + PC_ERR) || p_now() - t0s > kSpinTicks)) {
-                            if (l == 0 && !ld_sc1_u(a.ctl + PC_ERR) &&
-                                atomicCAS(a.ctl + PC_WHERE, 0u, wh(13) | ((unsigned)v << 19)) == 0u)
-                                a.ctl[PC_WHERE + 2] = (unsigned)t;
-                            if (l == 0) atomicMax(a.ctl + PC_ERR, 2u);
-                            fail = true;
-                            break;
-                        }
-                    }
+                    fail |= !poll_cand_couple(xr, pl, q_cand(cn, 2 * cul), QX_D * 4, want, a.ctl, wh(13), (unsigned)t,
+                                              false, q);
                     uint32_t bh = pl ? q.x : 0u, bl = pl ? q.y : 0u;
                     kmax_take(bh, bl, pl ? q.z : 0u, pl ? q.w : 0u);
                     row16_kmax(bh, bl);
                     const int bi = key_cls(bl);
-                    {
-#pragma clang fp contract(off)
-                        x = (2.0f * (float)bi) / (float)(a.n_classes - 1) - 1.0f;
-                    }
+                    x = bits_sample_of(bi, a.n_classes);
                     if (s == 0 && cell && cul == 0) {
                         int nn = cn;
                         asm volatile("" : "+v"(nn));
@@ -886,7 +818,7 @@ __global__ __launch_bounds__(256) void k_wide_rr_xbuf_reset(uint4* x) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)kPG * QX_GROUP / 4) return;
     const unsigned f = (unsigned)((i * 4) % QX_GROUP);
-    x[i] = f >= (unsigned)QX_D ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(kSentR, kSentR, kSentR, kSentR);
+    x[i] = f >= (unsigned)QX_D ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(kSent, kSent, kSent, kSent);
 }
 hipError_t persist_wide_rr_reset_xbuf(float* xbuf, hipStream_t s) {
     const unsigned n = (unsigned)((size_t)kPG * QX_GROUP / 4);

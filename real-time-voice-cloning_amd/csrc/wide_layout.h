@@ -24,7 +24,8 @@ constexpr int kBufs = 6;            // x1, h1, x2, h2, y1, y2
 constexpr int WX_D = kBufs * WV;    // candidates [n 16][slot 32] (value, tag|class)
 constexpr int WX_CAND = kRows * kSlots * 2;
 constexpr int WX_GROUP = WX_D + WX_CAND + 64;
-constexpr unsigned kNoOffset = 0x80000000u;  // lanes without a packet: outside every buffer
+// lanes without a packet: outside every buffer (the one value: persist_wide_common.h kNoOff is this)
+constexpr unsigned kNoOffset = 0x80000000u;
 constexpr unsigned kRsrcRecords = 0x7fffffffu;  // persist_common.h mk_rsrc num_records
 
 // consumer: byte offset (in a slot) of packet 0 of lane l of wave v; packet i at + 1 KiB i.

@@ -34,3 +34,23 @@ def test_dbg_instances_have_production_fp_arithmetic():
         a, b = isa_check.fp_hist(kern[prod]), isa_check.fp_hist(kern[dbg])
         assert sum(a.values()) > 50, prod
         assert a == b, (prod, {k: (a[k], b[k]) for k in set(a) | set(b) if a[k] != b[k]})
+
+
+@pytest.mark.skipif(not isa_check.tools_available() or not os.path.exists(isa_check.LIB),
+                    reason='ROCm LLVM tools or the built library missing')
+def test_wide_gen_ring_instances_do_not_spill():
+    """The planner silently drops a geneing wide ring / 32-row instance that needs scratch
+    (persist_wide_gen_ring_scratch(mode) == 0, persist_wide_gen32_usable: Beta at most its 16-byte
+    frame) and the call then runs, and passes its tests, on another launch kind. So the built
+    instances themselves are held to it: no scratch, no spilled VGPR."""
+    res = isa_check.resources_of(isa_check.LIB)
+    ring = {n: r for n, r in res.items()
+            if n.startswith('_ZN4wrnn18k_persist_wide_genILi') and 'ELb1ELb' in n.split('EEv')[0]}
+    gen32 = {n: r for n, r in res.items() if n.startswith('_ZN4wrnn20k_persist_wide_gen32ILi')}
+    # 3 heads x (production, DBG) each
+    assert len(ring) == 6 and len(gen32) == 6, (sorted(ring), sorted(gen32))
+    for name, r in {**ring, **gen32}.items():
+        beta = 'ILi2E' in name
+        assert r['private_segment_fixed_size'] <= (16 if beta else 0), (name, r)
+        assert r['vgpr_spill_count'] == 0, (name, r)
+        assert 0 < r['vgpr_count'] <= 256, (name, r)

@@ -36,28 +36,34 @@ FP = re.compile(r'^v_(?!cmp|cmpx|cndmask|mov|readlane|readfirstlane|writelane)'
 
 def tools_available():
     return all(os.path.exists(os.path.join(LLVM, t))
-               for t in ('llvm-objcopy', 'clang-offload-bundler', 'llvm-objdump'))
+               for t in ('llvm-objcopy', 'clang-offload-bundler', 'llvm-objdump', 'llvm-readelf'))
+
+
+def _code_objects(lib, tmp):
+    """Paths of the gfx950 code objects of the library (or object file), unbundled into tmp."""
+    fb = os.path.join(tmp, 'fatbin')
+    subprocess.run([os.path.join(LLVM, 'llvm-objcopy'), f'--dump-section=.hip_fatbin={fb}', lib,
+                    os.path.join(tmp, 'lib.copy')], check=True)
+    data = open(fb, 'rb').read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)] + [len(data)]
+    for i in range(len(starts) - 1):
+        part = os.path.join(tmp, f'b{i}')
+        with open(part, 'wb') as f:
+            f.write(data[starts[i]:starts[i + 1]])
+        co = part + '.co'
+        r = subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--unbundle', '--type=o',
+                            f'--input={part}', f'--targets={TARGET}', f'--output={co}'],
+                           capture_output=True)
+        if r.returncode or not os.path.exists(co) or os.path.getsize(co) == 0:
+            continue
+        yield co
 
 
 def kernels_of(lib):
     """{mangled kernel name: [opcode, ...]} over every gfx950 code object in the library."""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        fb = os.path.join(tmp, 'fatbin')
-        subprocess.run([os.path.join(LLVM, 'llvm-objcopy'), f'--dump-section=.hip_fatbin={fb}', lib,
-                        os.path.join(tmp, 'lib.copy')], check=True)
-        data = open(fb, 'rb').read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)] + [len(data)]
-        for i in range(len(starts) - 1):
-            part = os.path.join(tmp, f'b{i}')
-            with open(part, 'wb') as f:
-                f.write(data[starts[i]:starts[i + 1]])
-            co = part + '.co'
-            r = subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--unbundle', '--type=o',
-                                f'--input={part}', f'--targets={TARGET}', f'--output={co}'],
-                               capture_output=True)
-            if r.returncode or not os.path.exists(co) or os.path.getsize(co) == 0:
-                continue
+        for co in _code_objects(lib, tmp):
             dis = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', co], check=True,
                                  capture_output=True, text=True).stdout
             cur = None
@@ -70,6 +76,26 @@ def kernels_of(lib):
                 s = line.strip()
                 if cur and s[:2] in ('v_', 's_', 'ds', 'bu', 'gl', 'fl', 'sc'):
                     out[cur].append(s.split()[0])
+    return out
+
+
+RESOURCES = ('private_segment_fixed_size', 'vgpr_count', 'vgpr_spill_count', 'sgpr_spill_count')
+
+
+def resources_of(lib):
+    """{mangled kernel name: {resource: int}} for RESOURCES (scratch bytes, registers, spills), read
+    from the metadata notes of every gfx950 code object in the library (llvm-readelf --notes)."""
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in _code_objects(lib, tmp):
+            notes = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', co], check=True,
+                                   capture_output=True, text=True).stdout
+            # one "  - .agpr_count: ..." block per kernel, its keys sorted: one `.key: value` a line
+            for block in re.split(r'\n  - (?=\.)', notes)[1:]:
+                keys = dict(re.findall(r'^\s+\.(\w+):\s+(\S+)\s*$', block, re.M) +
+                            re.findall(r'^\.(\w+):\s+(\S+)\s*$', block, re.M))
+                if 'name' in keys and all(k in keys for k in RESOURCES):
+                    out[keys['name']] = {k: int(keys[k]) for k in RESOURCES}
     return out
 
 
