@@ -14,8 +14,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <sstream>
 #include <map>
 #include <memory>
 #include <string>
@@ -23,10 +21,9 @@
 #include <tuple>
 #include <vector>
 
-#include <dlfcn.h>
-
 #include "cand_key.h"
 #include "philox.h"
+#include "plan.h"
 #include "wavernn_mi355x.h"
 #include "wrnn_kernels.h"
 
@@ -115,60 +112,6 @@ struct StageDesc {
     int K;
     std::vector<SegDesc> segs;
     bool next_step_only;  // segment list index 1.. may be dropped at the last step (P1)
-};
-
-
-struct PlanRates {
-    double fat9[kPNR + 1] = {0, 4.8, 5.15, 5.91, 6.92};   // k_persist 9-bit (r05 nr_probe)
-    double fat10[kPNR + 1] = {0, 4.21, 5.19, 6.50, 9.41}; // 10-bit (profiles/r06/b u10_nr*)
-    // sparse instances (§3.0g): 9-bit measured (profiles/r06/b sp_nr*, 90 %-pruned weights);
-    // 10-bit = 9-bit + the dense 10-bit / 9-bit difference at 3-4 rows (estimate)
-    double fat9_sp[kPNR + 1] = {0, 4.99, 6.95, 7.99, 9.26};
-    double fat10_sp[kPNR + 1] = {0, 5.3, 7.3, 8.6, 11.7};
-    double rr[kPNR + 1] = {0, 6.7, 7.75, 8.81, 9.87};     // k_persist_rr (round 2, linear below 3)
-    double gen[kPNR + 1] = {0, 2.61, 3.26, 3.91, 4.56};   // k_persist_gen
-    // wide MFMA launches: base + row x r per step at r rows per group, + c10 at 1024 classes:
-    // 9.72 us at 16 rows (profiles/r05/final/c4.log, r06/b sp_c4), 10.965 at 16 rows / 1024
-    // classes (r05/final/b10.log), 10.59 at 6 rows / 1024 classes (r06/b u10_wide)
-    double wide[3] = {9.32, 0.025, 1.24};
-    // the MOL head on the wide kernel (fatchord): base + row x r. 9.43 / 9.57 / 9.65 us at 5 / 9 /
-    // 16 rows per group (profiles/wide_mol/mol_wide_r*.log, least squares: tools/make_rates.py)
-    double wide_mol[2] = {9.366, 0.0185};
-    double wide_rr[2] = {12.0, 0.025};                     // 12.39 us at 15-16 rows (r04 wide_rr)
-    // the MOL head on the runtimeracer wide kernel: base + row x r. 9.43 / 9.60 / 9.79 us at 5 / 9 /
-    // 16 rows per group (profiles/wide_rr_mol/rr_mol_wide_r*.log, least squares:
-    // tools/make_rates.py)
-    double wide_rr_mol[2] = {9.285, 0.0321};
-    // geneing BITS on its wide kernel (kernels_persist_wide_gen.hip): base + row x r. 3.540 /
-    // 3.594 / 3.634 us at 5 / 9 / 16 rows per group (profiles/wide_gen/gen_wide_r*.log, least
-    // squares: tools/make_rates.py)
-    double wide_gen[2] = {3.508, 0.0082};
-    // the geneing continuous heads on the same kernel, base + row x r: MOL (30 logits) 3.067 /
-    // 3.116 / 3.172 us, Beta (2 logits, float64 gamma draws) 4.993 / 5.156 / 5.361 us at 5 / 9 / 16
-    // rows per group (profiles/wide_gen_mol/gen_{mol,beta}_wide_r*.log, least squares:
-    // tools/make_rates.py)
-    double wide_gen_mol[2] = {3.025, 0.0094};
-    double wide_gen_beta[2] = {4.84, 0.033};
-    // the 32-row ring instances of that kernel (k_persist_wide_gen32; launches of 17 .. 32 rows per
-    // group, wrnn_set_gen_wide_rows(32)), base + row x r: BITS 6.476 / 6.464 / 6.555 us, MOL 4.411 /
-    // 4.422 / 4.677 us, Beta 7.413 / 7.932 / 8.415 us at 17 / 23 / 29 rows per group
-    // (profiles/wide_gen32/gen32_{,mol_,beta_}wide_r*.log, least squares: tools/make_rates.py)
-    double wide_gen32[2] = {6.347, 0.0066};
-    double wide_gen32_mol[2] = {3.992, 0.0222};
-    double wide_gen32_beta[2] = {6.001, 0.0835};
-    double slice[2] = {60.0, 0.98};                        // us per extra launch, gain threshold
-    // rotation: rates of the rotated instance's two bodies by rows per group (the (q + 1)-row
-    // one at its single-launch rate; the q-row one the best split measured, §3.0e)
-    double rot9[kPNR + 1] = {0, 4.8, 5.22, 5.91, 6.92};
-    double rot9_sp[kPNR + 1] = {0, 4.99, 6.95, 7.99, 9.26};  // sparse (r06/b sp_nr*)
-    double rot_mol3_lo = 4.70;                             // MOL 3-row split (r05 rotation scan)
-    double rot_rr9[kPNR + 1] = {0, 6.3, 7.0, 7.78, 8.8};   // (2 / 4 rows: estimates)
-    double rot_rr10[kPNR + 1] = {0, 6.5, 7.26, 8.14, 9.23};  // profiles/r05/rr_rates/
-    double rot_rrm[kPNR + 1] = {0, 5.9, 6.6, 7.42, 8.4};   // profiles/r05/rr_rotation/mol/
-    double rot_gen[kPNR + 1] = {0, 1.98, 2.47, 3.12, 3.64};  // profiles/r05/gen_rotation/
-    double rot_genm[kPNR + 1] = {0, 1.72, 2.15, 2.60, 3.03};
-    double rot[2] = {40.0, 0.98};                          // us per extra launch, gain threshold
-    std::string source = "built-in defaults";
 };
 
 }  // namespace
@@ -293,25 +236,8 @@ struct wrnn_handle {
     unsigned* prog_host = nullptr;  // host-mapped progress word (kernels publish steps done)
     unsigned* prog_dev = nullptr;
     int last_Bp = 0;                // rows the last call ran (padded to 8 * rows-per-group)
-    struct PLaunch {
-        int rb, nr;  // first row, rows per XCD group (the launch runs rows rb + g + 8 r, r < nr)
-        bool wide;   // kernels_persist_wide.hip (MFMA) or the register-resident kernel
-        int rot = -1;  // launch j of the call's row rotation (rot_plan), or -1
-    };
-    // Row rotation of the last call: per launch j the virtual-row map
-    // (physical row, step offset), rows and steps per group, and the launch's RowInfo table
-    struct RotPlan {
-        int K = 0, nr_hi = 0, n_hi = 0, n_lo = 0;
-        std::vector<int2> vmap;     // [K][kPG * nr_hi]
-        std::vector<int> gnr, git;  // [K][kPG]
-    } rot_plan;
-    // Time-sliced wide launches of the last call: per launch the rows per group,
-    // the steps and the virtual-row map (physical row, step offset), by virtual row g + 8 r
-    struct WLaunch {
-        int nr, steps;
-        std::vector<int2> vmap;  // [kPG * nr]
-    };
-    std::vector<WLaunch> wrot;
+    RotPlan rot_plan;               // row rotation of the last call (plan.h)
+    std::vector<WLaunch> wrot;      // time-sliced wide launches of the last call (§3.0f)
     std::vector<PLaunch> p_plan;    // PERSIST: the launches of the last call, in order
     std::vector<int> pev_kind;      // per timed launch: 1 wide, 0 otherwise
     std::vector<int> pev_rows;      // per timed launch: rows (8 nr)
@@ -1991,7 +1917,6 @@ int run_chain(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
     return WRNN_OK;
 }
 
-constexpr double kPersistWsBytes = 96.0 * (1 << 30);  // P1 + cI + noise cap (of 288 GB HBM)
 constexpr int kPersistFallback = 1;  // internal: retry the call on the CHAIN engine
 constexpr int kPersistMaxStreak = 3; // consecutive failed persistent calls before AUTO stops trying
 
@@ -2090,122 +2015,6 @@ void persist_wide_rr_phase_report(wrnn_handle* h, int t) {
                          d[d.size() / 2], d.back());
         }
     }
-}
-
-// Row rotation. R fold rows on the 8 XCD groups of one register-resident
-// launch leave m = R % 8 groups with q + 1 rows and 8 - m with q: every group pays the
-// (q + 1)-row step (a padding row costs as much as a real one), so the launch runs S steps at
-// t(q + 1). Rotating the rows through the q + 1-row groups over K launches -- each row spends
-// h_c of them in a q + 1-row group and l_c in a q-row group, a group of q rows running its own
-// q-row body (the rotated kernel instance holds both) -- lets every group run at its own rate:
-// a q + 1-row group runs n_hi steps, a q-row group n_lo, n_hi t(q + 1) ~ n_lo t(q), and
-// h_c n_hi + l_c n_lo = S for every row. A row's state crosses launches through the chunk state
-// (st_*); its noise, labels and frames are read at its own step (the map's offset).
-// C2 (18 rows): 3 launches, 3672 steps at 3 rows / 4214 at 2 -> 65.1 ms instead of 71.5.
-static int gcd_i(int a, int b) { return b ? gcd_i(b, a % b) : a; }
-
-bool plan_rotation(int R, int S, double t_hi, double t_lo, wrnn_handle::RotPlan& P, double launch_us = 40.0,
-                   double gain = 0.98) {
-    P = wrnn_handle::RotPlan();
-    const int q = R / kPG, m = R % kPG;
-    if (q < 1 || m == 0 || q + 1 > 3 || S < 64) return false;
-    const int H = m * (q + 1), gg = gcd_i(R, H), K = R / gg, hc = H / gg, lc = K - hc;
-    if (K > 24 || lc < 1) return false;
-    // n_hi t_hi = n_lo t_lo and hc n_hi + lc n_lo = S, in integers
-    const double nh0 = S / (hc + lc * t_hi / t_lo);
-    int nh = -1, nl = -1;
-    for (int d = 0; d <= lc && nh < 0; ++d)
-        for (int sgn = -1; sgn <= 1 && nh < 0; sgn += 2) {
-            const int c = (int)std::lround(nh0) + sgn * d;
-            if (c >= 1 && (S - hc * c) > 0 && (S - hc * c) % lc == 0) {
-                nh = c;
-                nl = (S - hc * c) / lc;
-            }
-        }
-    if (nh < 1 || nl < 1) return false;
-    // worth it? (an extra launch reloads the weights: ~40 us)
-    const double rot = K * std::max(nh * t_hi, nl * t_lo) + (K - 1) * launch_us, plain = S * t_hi;
-    if (rot > gain * plain) return false;
-    P.K = K;
-    P.nr_hi = q + 1;
-    P.n_hi = nh;
-    P.n_lo = nl;
-    P.vmap.assign((size_t)K * kPG * (q + 1), make_int2(0, 0));
-    P.gnr.assign((size_t)K * kPG, 0);
-    P.git.assign((size_t)K * kPG, 0);
-    std::vector<int> off(R, 0);
-    for (int j = 0; j < K; ++j) {
-        std::vector<char> hi(R, 0);
-        std::vector<int> his, los;
-        for (int i = 0; i < H; ++i) hi[(j * gg + i) % R] = 1;
-        for (int i = 0; i < H; ++i) his.push_back((j * gg + i) % R);
-        for (int r = 0; r < R; ++r)
-            if (!hi[r]) los.push_back(r);
-        for (int g = 0; g < kPG; ++g) {
-            const bool gh = g < m;
-            const int nr = gh ? q + 1 : q;
-            P.gnr[(size_t)j * kPG + g] = nr;
-            P.git[(size_t)j * kPG + g] = gh ? nh : nl;
-            for (int r = 0; r < nr; ++r) {
-                const int row = gh ? his[(size_t)g * (q + 1) + r] : los[(size_t)(g - m) * q + r];
-                P.vmap[(size_t)j * kPG * (q + 1) + g + kPG * r] = make_int2(row, off[row]);
-            }
-        }
-        for (int r = 0; r < R; ++r) off[r] += hi[r] ? nh : nl;
-    }
-    for (int r = 0; r < R; ++r)
-        if (off[r] != S) return (P = wrnn_handle::RotPlan(), false);
-    return true;
-}
-
-// Time-sliced wide launches. The wide kernel's step costs nearly the same for
-// any row count up to 16 per group (MFMA tiles of 16 columns), so R = 8 R_g rows with R_g > 16
-// (not a multiple of 16; at most 64 launches) run best as launches of 16 rows per group over
-// rotating row sets: with
-// d = R_g - 16 rows of each group idle per launch (a circular shift by gcd(R_g, d) rows per
-// launch), K = R_g / gcd launches make every row active in A = 16 K / R_g of them; each runs
-// n = S / A steps (integer part), and ceil(R_g / 16) short launches give every row the remaining
-// S - A n. C4 (144 rows, 18 per group): 9 launches of 1,512 steps + 2 of 4 -- 1.125 S wide steps
-// instead of S wide steps + S steps of a 2-row register-resident launch for the 16 rows left over.
-bool plan_wide_slices(int R, int S, std::vector<wrnn_handle::WLaunch>& out) {
-    out.clear();
-    if (R % kPG) return false;
-    const int Rg = R / kPG;
-    if (Rg <= kPWideRows || Rg % kPWideRows == 0) return false;  // (a multiple of 16: full launches)
-    const int d = Rg - kPWideRows, gg = gcd_i(Rg, d), K = Rg / gg, A = kPWideRows * K / Rg;
-    if (K > 64) return false;
-    const int n = S / A, rem = S - A * n;
-    if (n < 64) return false;
-    std::vector<int> off(R, 0);
-    for (int j = 0; j < K; ++j) {
-        std::vector<char> idle(Rg, 0);
-        for (int k = 0; k < d; ++k) idle[(j * gg + k) % Rg] = 1;
-        wrnn_handle::WLaunch L{kPWideRows, n, std::vector<int2>((size_t)kPG * kPWideRows)};
-        for (int g = 0; g < kPG; ++g) {
-            int r = 0;
-            for (int i = 0; i < Rg; ++i)
-                if (!idle[i]) {
-                    const int row = g + kPG * i;
-                    L.vmap[(size_t)g + kPG * r++] = make_int2(row, off[row]);
-                    off[row] += n;
-                }
-        }
-        out.push_back(std::move(L));
-    }
-    for (int k = 0; rem > 0 && k * kPWideRows < Rg; ++k) {  // the remaining steps of every row
-        const int nr = std::min(kPWideRows, Rg - k * kPWideRows);
-        wrnn_handle::WLaunch L{nr, rem, std::vector<int2>((size_t)kPG * nr)};
-        for (int g = 0; g < kPG; ++g)
-            for (int r = 0; r < nr; ++r) {
-                const int row = g + kPG * (k * kPWideRows + r);
-                L.vmap[(size_t)g + kPG * r] = make_int2(row, off[row]);
-                off[row] += rem;
-            }
-        out.push_back(std::move(L));
-    }
-    for (int r = 0; r < R; ++r)
-        if (off[r] != S) return (out.clear(), false);
-    return true;
 }
 
 // PERSIST engine: P1 for all steps (one MFMA GEMM), Gumbel noise (RAW), step-0 state, then
@@ -2464,7 +2273,7 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             if (!L.wide && L.nr != RP.nr_hi)
                 return fail(WRNN_ERR_INVALID, "rotated launch with " + std::to_string(L.nr) +
                                                    " rows per group, rotation plan of " + std::to_string(RP.nr_hi));
-        auto nv_of = [&](const wrnn_handle::PLaunch& L) { return kPG * (L.wide ? h->wrot[L.rot].nr : RP.nr_hi); };
+        auto nv_of = [&](const PLaunch& L) { return kPG * (L.wide ? h->wrot[L.rot].nr : RP.nr_hi); };
         size_t total = 0;
         for (const auto& L : h->p_plan) {
             rot_off.push_back(total);
@@ -2476,7 +2285,11 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             const auto& L = h->p_plan[b];
             const int nv = nv_of(L);
             char* base = h->rot_host.data() + rot_off[b];
-            const int2* vm = L.wide ? h->wrot[L.rot].vmap.data() : &RP.vmap[(size_t)L.rot * nv];
+            const VRow* vm = L.wide ? h->wrot[L.rot].vmap.data() : &RP.vmap[(size_t)L.rot * nv];
+            // the kernels read the planner's maps as int2 (row = x, off = y)
+            static_assert(sizeof(VRow) == sizeof(int2) && offsetof(VRow, row) == offsetof(int2, x) &&
+                              offsetof(VRow, off) == offsetof(int2, y),
+                          "VRow must have int2's layout");
             std::memcpy(base, vm, (size_t)nv * sizeof(int2));
             int* gi = reinterpret_cast<int*>(base + (size_t)nv * sizeof(int2));
             if (!L.wide) {
@@ -2485,8 +2298,8 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             }
             RowInfo* rv = reinterpret_cast<RowInfo*>(gi + 2 * kPG);
             for (int v = 0; v < nv; ++v) {
-                rv[v] = h->rows_host[vm[v].x];
-                rv[v].rel0 += vm[v].y;
+                rv[v] = h->rows_host[vm[v].row];
+                rv[v].rel0 += vm[v].off;
             }
         }
         CHECK(P.rot.alloc(h->rot_host.size()));
@@ -2786,447 +2599,6 @@ int setup_debug_logits(wrnn_handle* h, int S, int Bp) {
     return WRNN_OK;
 }
 
-// ===== Launch-plan rates ==================================================
-// Per-step costs (us, MI355X) the launch planner minimises. The defaults are the measured
-// points of the rounds cited beside them; a measurement pass emits a per-build table
-// (tools/make_rates.py -> wavernn_amd/rates_mi355x.txt next to the library, or the file named
-// by env WRNN_RATES) that replaces them key by key at wrnn_create. Format: one key per line,
-// `name v1 v2 ...`, '#' comments; by rows per group 1..4 for the register-resident tables.
-struct RateKey {
-    const char* name;
-    double PlanRates::*one;
-    double (PlanRates::*arr5)[kPNR + 1];
-    double (PlanRates::*arr3)[3];
-    double (PlanRates::*arr2)[2];
-};
-static const RateKey kRateKeys[] = {
-    {"fat9", nullptr, &PlanRates::fat9, nullptr, nullptr},
-    {"fat10", nullptr, &PlanRates::fat10, nullptr, nullptr},
-    {"fat9_sp", nullptr, &PlanRates::fat9_sp, nullptr, nullptr},
-    {"fat10_sp", nullptr, &PlanRates::fat10_sp, nullptr, nullptr},
-    {"rr", nullptr, &PlanRates::rr, nullptr, nullptr},
-    {"gen", nullptr, &PlanRates::gen, nullptr, nullptr},
-    {"wide", nullptr, nullptr, &PlanRates::wide, nullptr},
-    {"wide_mol", nullptr, nullptr, nullptr, &PlanRates::wide_mol},
-    {"wide_rr", nullptr, nullptr, nullptr, &PlanRates::wide_rr},
-    {"wide_rr_mol", nullptr, nullptr, nullptr, &PlanRates::wide_rr_mol},
-    {"wide_gen", nullptr, nullptr, nullptr, &PlanRates::wide_gen},
-    {"wide_gen_mol", nullptr, nullptr, nullptr, &PlanRates::wide_gen_mol},
-    {"wide_gen_beta", nullptr, nullptr, nullptr, &PlanRates::wide_gen_beta},
-    {"wide_gen32", nullptr, nullptr, nullptr, &PlanRates::wide_gen32},
-    {"wide_gen32_mol", nullptr, nullptr, nullptr, &PlanRates::wide_gen32_mol},
-    {"wide_gen32_beta", nullptr, nullptr, nullptr, &PlanRates::wide_gen32_beta},
-    {"slice", nullptr, nullptr, nullptr, &PlanRates::slice},
-    {"rot9", nullptr, &PlanRates::rot9, nullptr, nullptr},
-    {"rot9_sp", nullptr, &PlanRates::rot9_sp, nullptr, nullptr},
-    {"rot_mol3_lo", &PlanRates::rot_mol3_lo, nullptr, nullptr, nullptr},
-    {"rot_rr9", nullptr, &PlanRates::rot_rr9, nullptr, nullptr},
-    {"rot_rr10", nullptr, &PlanRates::rot_rr10, nullptr, nullptr},
-    {"rot_rrm", nullptr, &PlanRates::rot_rrm, nullptr, nullptr},
-    {"rot_gen", nullptr, &PlanRates::rot_gen, nullptr, nullptr},
-    {"rot_genm", nullptr, &PlanRates::rot_genm, nullptr, nullptr},
-    {"rot", nullptr, nullptr, nullptr, &PlanRates::rot},
-};
-
-// Overrides the keys a table names (unknown keys and malformed lines are errors; values must
-// be positive). The register-resident tables take 1-4 values (rows per group 1..4).
-bool parse_rates(const char* text, PlanRates& R, std::string& err) {
-    std::istringstream in(text ? text : "");
-    std::string line;
-    int ln = 0;
-    while (std::getline(in, line)) {
-        ++ln;
-        const size_t hash = line.find('#');
-        if (hash != std::string::npos) line.resize(hash);
-        std::istringstream ls(line);
-        std::string key;
-        if (!(ls >> key)) continue;
-        std::vector<double> v;
-        double x;
-        while (ls >> x) v.push_back(x);
-        if (!ls.eof()) return err = "line " + std::to_string(ln) + ": not a number", false;
-        const RateKey* k = nullptr;
-        for (const auto& e : kRateKeys)
-            if (key == e.name) k = &e;
-        if (!k) return err = "line " + std::to_string(ln) + ": unknown key '" + key + "'", false;
-        for (double d : v)
-            if (!(d > 0)) return err = "line " + std::to_string(ln) + ": values must be > 0", false;
-        const size_t want = k->one ? 1 : k->arr5 ? kPNR : k->arr3 ? 3 : 2;
-        if (v.size() != want)
-            return err = "line " + std::to_string(ln) + ": '" + key + "' takes " + std::to_string(want) + " values",
-                   false;
-        if (k->one) R.*(k->one) = v[0];
-        for (size_t i = 0; i < v.size(); ++i) {
-            if (k->arr5) (R.*(k->arr5))[i + 1] = v[i];
-            if (k->arr3) (R.*(k->arr3))[i] = v[i];
-            if (k->arr2) (R.*(k->arr2))[i] = v[i];
-        }
-    }
-    return true;
-}
-
-std::string rates_text(const PlanRates& R) {
-    std::ostringstream o;
-    o << "# source: " << R.source << "\n";
-    for (const auto& k : kRateKeys) {
-        o << k.name;
-        if (k.one) o << ' ' << R.*(k.one);
-        if (k.arr5)
-            for (int i = 1; i <= kPNR; ++i) o << ' ' << (R.*(k.arr5))[i];
-        if (k.arr3)
-            for (int i = 0; i < 3; ++i) o << ' ' << (R.*(k.arr3))[i];
-        if (k.arr2)
-            for (int i = 0; i < 2; ++i) o << ' ' << (R.*(k.arr2))[i];
-        o << '\n';
-    }
-    return o.str();
-}
-
-// The table a new handle plans with: the defaults, then WRNN_RATES (a path) or the
-// rates_mi355x.txt beside this library when present. A file that does not parse is reported on
-// stderr and ignored (the defaults stay).
-PlanRates load_rates() {
-    PlanRates R;
-    std::string path;
-    if (const char* e = std::getenv("WRNN_RATES")) {
-        path = e;
-    } else {
-        Dl_info di;
-        if (dladdr(reinterpret_cast<void*>(&load_rates), &di) && di.dli_fname) {
-            std::string so = di.dli_fname;
-            const size_t sl = so.rfind('/');
-            path = (sl == std::string::npos ? std::string(".") : so.substr(0, sl)) + "/rates_mi355x.txt";
-        }
-    }
-    if (path.empty()) return R;
-    std::ifstream f(path);
-    if (!f) return R;
-    std::stringstream ss;
-    ss << f.rdbuf();
-    PlanRates T = R;
-    std::string err;
-    if (!parse_rates(ss.str().c_str(), T, err)) {
-        std::fprintf(stderr, "[wavernn-mi355x] WARNING: rate table %s ignored: %s\n", path.c_str(), err.c_str());
-        return R;
-    }
-    T.source = path;
-    return T;
-}
-
-// Inputs of one call's launch plan: the model, the call's rows / steps, which kernel variants
-// exist and spill (scratch bytes, -1 = no such variant) and the env switches. generate_impl
-// fills it from the handle and the device; wrnn_debug_plan from its arguments (spill-free).
-struct PlanIn {
-    bool ok = false, fat = false, rr = false, gen = false;
-    int mode = 0, n = 0, cpw = 0, B = 0, S = 0;
-    bool c10 = false, sp = false, p1ring = false, rr_frames = false;
-    bool force_sp = false;  // env WRNN_SPARSE=1: the sparse instances whatever the rates
-    bool has_wide = false, has_wide_rr = false;  // (has_wide: RAW or MOL images; has_wide_rr: RAW only)
-    bool has_wide_rr_mol = false;  // runtimeracer MOL image (30 logits)
-    bool has_wide_gen = false;     // geneing BITS image (512 / 1024 classes)
-    bool has_wide_gen_mol = false;   // geneing MOL image (30 logits)
-    bool has_wide_gen_beta = false;  // geneing Beta image (2 logits)
-    // geneing: the head's 32-row ring instances are selected (wrnn_set_gen_wide_rows / env
-    // WRNN_GEN_WIDE_ROWS) and can run -- spill-free, and the call can take the ring (the per-frame
-    // P1 form exists, WRNN_GEN_RING is not 0): established before a 32-row launch is priced
-    bool gen32 = false;
-    int scr[2][kPNR + 1] = {};     // fatchord k_persist [stream | ring][nr]
-    int scr_sp[kPNR + 1] = {};     // sparse instances
-    int scr_rot[2][kPNR + 1] = {}; // rotated instance of this topology / mode [dense | sparse][nr]
-    bool ok_reg[kPNR + 1] = {};    // runtimeracer / geneing register-resident variants
-    int wide_scr = 0, wide_rot_scr = 0;
-    // env switches
-    int wmode = 2, nr_max = 0;
-    bool slice_off = false, rot_off = false, allow_wide_scratch = false;
-    double rot_hi = 0, rot_lo = 0;  // WRNN_ROT_US (rate A/B); 0: none
-};
-struct PlanOut {
-    std::vector<wrnn_handle::PLaunch> lplan;
-    double plan_us = 0;
-    std::vector<wrnn_handle::WLaunch> wrot;
-    wrnn_handle::RotPlan rot;
-    bool p1_ring = false, sparse = false;
-    int Bplan = 0;
-};
-
-// The persistent launch plan (consecutive launches over row batches; launch k runs rows
-// rb_k + g + 8 r, r < nr_k, in every XCD group g): the cheapest mix of register-resident
-// (nr <= 4, spill-free variants) and wide MFMA launches (nr <= 16; geneing with 32 rows selected:
-// nr <= 32 in plans of wide launches only) by the per-step rates, then
-// time-sliced wide launches (§3.0f) or a row rotation (§3.0e) when those are cheaper.
-void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
-    out = PlanOut();
-    const int B = in.B, S = in.S;
-    // per-step cost of a fatchord wide launch of r rows per group
-    const bool mol = in.mode == WRNN_MODE_MOL;
-    auto wide_us = [&](int r) {
-        return mol ? R.wide_mol[0] + R.wide_mol[1] * r : R.wide[0] + R.wide[1] * r + (in.c10 ? R.wide[2] : 0.0);
-    };
-    // ... and of a runtimeracer one
-    auto wide_rr_us = [&](int r) {
-        return mol ? R.wide_rr_mol[0] + R.wide_rr_mol[1] * r : R.wide_rr[0] + R.wide_rr[1] * r;
-    };
-    // a wide MOL launch indexes the k_mol_noise stream ([S][rows][kMolNoise], rows padded to a
-    // launch) in 32 bits: it must stay below 2 GiB (launch_persist_wide and
-    // launch_persist_wide_rr refuse it otherwise)
-    const bool wide_fits = !mol || (double)S * (B + kPG * kPWideRows) * kMolNoise * 4.0 < 2147483648.0;
-    // runtimeracer MOL: wide launches only for calls no single register-resident launch holds
-    // (more than 32 rows), so every plan of at most 32 rows stays as it was; WRNN_PERSIST_WIDE=1
-    // forces them at any size (as geneing below)
-    const bool rr_mol_wide = in.rr && in.has_wide_rr_mol && mol && wide_fits && (in.wmode == 1 || B > kPG * kPNR);
-    struct Opt {
-        int nr;
-        bool wide;
-        double us;
-    };
-    // sparse k_persist instances compete with the dense ones by their own rates: the cheaper
-    // register-resident family wins the call (both give the same results, §3.0g)
-    bool use_sp = false;
-    if (in.ok && in.fat && in.sp) {
-        const double* us = in.c10 ? R.fat10 : R.fat9;
-        const double* us_sp = in.c10 ? R.fat10_sp : R.fat9_sp;
-        double best_d = 1e300, best_s = 1e300;
-        for (int c = 1; c <= kPNR; ++c) {
-            const int rows = kPG * c, n_l = (B + rows - 1) / rows;  // launches of c rows per group
-            int sc = in.scr[0][c];
-            if (in.p1ring && in.scr[1][c] >= 0 && (sc < 0 || in.scr[1][c] < sc)) sc = in.scr[1][c];
-            if (sc >= 0 && sc <= 64) best_d = std::min(best_d, n_l * us[c]);
-            if (in.scr_sp[c] >= 0 && in.scr_sp[c] <= 64) best_s = std::min(best_s, n_l * us_sp[c]);
-        }
-        use_sp = in.force_sp || best_s < best_d;
-    }
-    if (in.ok) {
-        std::vector<Opt> opts;
-        bool gen_wide = false;  // geneing: this call's head is offered wide launches
-        if (in.fat) {
-            const double* us = in.c10 ? R.fat10 : R.fat9;
-            const double* us_sp = in.c10 ? R.fat10_sp : R.fat9_sp;
-            for (int c = 1; c <= kPNR; ++c) {
-                if (use_sp) {
-                    if (in.scr_sp[c] >= 0 && in.scr_sp[c] <= 64) opts.push_back({c, false, us_sp[c]});
-                    continue;
-                }
-                int sc = in.scr[0][c];
-                if (in.p1ring) {  // the call uses the flavour that spills less (below)
-                    const int sr = in.scr[1][c];
-                    if (sr >= 0 && (sc < 0 || sr < sc)) sc = sr;
-                }
-                if (sc >= 0 && sc <= 64) opts.push_back({c, false, us[c]});
-            }
-            if (in.wmode && in.has_wide && wide_fits && (in.wide_scr == 0 || in.allow_wide_scratch)) {
-                if (in.wmode == 1) opts.clear();
-                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, wide_us(r)});
-            }
-        } else {
-            for (int r = 1; r <= kPNR; ++r)
-                if (in.ok_reg[r]) opts.push_back({r, false, in.gen ? R.gen[r] : R.rr[r]});
-            if (in.rr && ((in.has_wide_rr && in.mode == WRNN_MODE_RAW) || rr_mol_wide) && in.wmode &&
-                (in.wide_scr == 0 || in.allow_wide_scratch)) {
-                if (in.wmode == 1) opts.clear();
-                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, wide_rr_us(r)});
-            }
-            // geneing BITS: wide launches only for calls no single register-resident launch
-            // holds (more than 32 rows), so every plan of at most 32 rows stays as it was;
-            // WRNN_PERSIST_WIDE=1 forces them at any size
-            if (in.gen && in.has_wide_gen && in.mode == WRNN_MODE_RAW && in.wmode &&
-                (in.wmode == 1 || B > kPG * kPNR) && (in.wide_scr == 0 || in.allow_wide_scratch)) {
-                if (in.wmode == 1) opts.clear();
-                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, R.wide_gen[0] + R.wide_gen[1] * r});
-                gen_wide = true;
-            }
-            // geneing MOL / Beta: the same rule, each head by its own image and its own key (the
-            // MOL instances run spill-free; the Beta ones may keep the frame k_persist_gen BETA is
-            // accepted with, at most 16 bytes)
-            const bool gen_mol = in.gen && in.has_wide_gen_mol && in.mode == WRNN_MODE_MOL;
-            const bool gen_beta = in.gen && in.has_wide_gen_beta && in.mode == WRNN_MODE_BETA;
-            if ((gen_mol || gen_beta) && in.wmode && (in.wmode == 1 || B > kPG * kPNR) &&
-                ((in.wide_scr >= 0 && in.wide_scr <= (gen_beta ? 16 : 0)) || in.allow_wide_scratch)) {
-                const double* k = gen_mol ? R.wide_gen_mol : R.wide_gen_beta;
-                if (in.wmode == 1) opts.clear();
-                for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, k[0] + k[1] * r});
-                gen_wide = true;
-            }
-        }
-        if (in.nr_max > 0) {  // diagnostic: variant A/B (WRNN_PERSIST_NR_MAX)
-            const int c = std::max(1, std::min(kPNR, in.nr_max));
-            opts.erase(std::remove_if(opts.begin(), opts.end(), [&](const Opt& o) { return o.wide || o.nr != c; }),
-                       opts.end());
-            if (opts.empty()) opts.push_back({c, false, 1.0});
-        }
-        // the cheapest sequence of launches from `opts` over the call's rows
-        auto solve = [&](const std::vector<Opt>& opts, std::vector<wrnn_handle::PLaunch>& lplan) {
-            // best[r]: cheapest plan for r rows; pick[r]: its first launch
-            std::vector<double> best(B + 1, 0.0);
-            std::vector<int> pick(B + 1, -1);
-            for (int r = 1; r <= B; ++r) {
-                best[r] = 1e300;
-                for (int o = 0; o < (int)opts.size(); ++o) {
-                    const double c = opts[o].us + best[std::max(0, r - kPG * opts[o].nr)];
-                    if (c < best[r] - 1e-9) {
-                        best[r] = c;
-                        pick[r] = o;
-                    }
-                }
-            }
-            int rb = 0;
-            for (int r = B; r > 0;) {
-                const Opt& o = opts[pick[r]];
-                lplan.push_back({rb, o.nr, o.wide});
-                rb += kPG * o.nr;
-                r = std::max(0, r - kPG * o.nr);
-            }
-            return best[B];
-        };
-        if (!opts.empty()) out.plan_us = solve(opts, out.lplan);
-        // geneing, 32 rows selected: the 32-row ring instances read no stream, so they enter only
-        // plans whose launches are all wide -- the cheapest all-wide plan over 1 .. 32 rows per
-        // group (launches of at most 16 on the existing instances, by their own keys) replaces the
-        // plan above when it is cheaper. The MOL draw stream is padded to the 32-row launch
-        if (in.gen && in.gen32 && gen_wide && in.nr_max <= 0 && !out.lplan.empty() &&
-            (!mol || (double)S * (B + kPG * kPWideGen32Rows) * kMolNoise * 4.0 < 2147483648.0)) {
-            const double* k = in.mode == WRNN_MODE_RAW ? R.wide_gen32
-                            : in.mode == WRNN_MODE_MOL ? R.wide_gen32_mol : R.wide_gen32_beta;
-            std::vector<Opt> wopts;
-            for (const Opt& o : opts)
-                if (o.wide) wopts.push_back(o);
-            for (int r = kPWideRows + 1; r <= kPWideGen32Rows; ++r) wopts.push_back({r, true, k[0] + k[1] * r});
-            std::vector<wrnn_handle::PLaunch> lp32;
-            const double us32 = solve(wopts, lp32);
-            if (us32 < out.plan_us - 1e-9) {
-                out.lplan = std::move(lp32);
-                out.plan_us = us32;
-            }
-        }
-    }
-    // time-sliced wide launches, when cheaper than the plan above by the same rates (P1 formed
-    // in-kernel: fatchord RAW up to 1024 classes and MOL, runtimeracer RAW and MOL)
-    const bool fat_sl = in.ok && in.fat && in.has_wide && in.p1ring && wide_fits &&
-                        (in.mode == WRNN_MODE_RAW || mol);
-    const bool rr_sl = in.ok && in.rr && in.rr_frames &&
-                       ((in.has_wide_rr && in.mode == WRNN_MODE_RAW) || rr_mol_wide);
-    if ((fat_sl || rr_sl) && !out.lplan.empty() && !in.slice_off && in.wmode && in.wide_rot_scr == 0) {
-        std::vector<wrnn_handle::WLaunch> sl;
-        if (plan_wide_slices(B, S, sl)) {
-            double cost = R.slice[0] * (sl.size() - 1);  // (an extra launch: weights, ring prologue)
-            for (const auto& L : sl)
-                cost += L.steps * (fat_sl ? wide_us(L.nr) : wide_rr_us(L.nr));
-            if (cost < R.slice[1] * out.plan_us * S) {
-                out.lplan.clear();
-                for (int j = 0; j < (int)sl.size(); ++j) out.lplan.push_back({0, sl[j].nr, true, j});
-                out.wrot = std::move(sl);
-            }
-        }
-    }
-    const auto& lp = out.lplan;
-    out.Bplan = lp.empty() ? B : !out.wrot.empty() ? B : lp.back().rb + kPG * lp.back().nr;
-    // P1 ring (fatchord): on unless a register-resident launch spills more with it than with the
-    // stream (MOL at 3 rows per group: one register, 6.87 against 6.53 us per step); the sparse
-    // instances exist with the ring only
-    out.p1_ring = in.p1ring;
-    bool any_reg = false;
-    for (const auto& L : lp) any_reg |= !L.wide;
-    if (use_sp && any_reg) {
-        out.sparse = true;
-    } else if (in.fat) {
-        for (const auto& L : lp)
-            if (out.p1_ring && !L.wide && in.scr[1][L.nr] > in.scr[0][L.nr]) out.p1_ring = false;
-    }
-    // row rotation: one register-resident launch with uneven groups becomes K launches over
-    // rotating row sets. plan_rotation derives its (q + 1)-row body from B, so the launch must
-    // run exactly ceil(B / 8) rows per group; every rotated kernel forms its noise offsets in
-    // 32 bits, so the padded noise stream must stay below 4 GB
-    if (lp.size() != 1 || lp[0].wide || lp[0].nr != (B + kPG - 1) / kPG) return;
-    if (!((double)S * out.Bplan * in.n * 4.0 < 4.0e9) || in.rot_off) return;
-    if (in.mode != WRNN_MODE_RAW && in.mode != WRNN_MODE_MOL) return;
-    const int nr = lp[0].nr;
-    const bool fat_rot = in.fat && out.p1_ring && in.cpw <= 16;
-    if (nr < 2 || !(fat_rot || in.rr || in.gen)) return;
-    double t_hi, t_lo;
-    if (in.fat) {
-        const double* u = out.sparse ? R.rot9_sp : R.rot9;
-        t_hi = u[nr];
-        t_lo = u[nr - 1];
-        // MOL: its rotated 3-row body (one spilled register) runs much slower than the 2-row
-        // one -- the split balanced for 5.91 / 4.70 is the fastest of a scan (C3 5.61 -> 5.19)
-        if (in.mode == WRNN_MODE_MOL && nr == 3 && !out.sparse) t_lo = R.rot_mol3_lo;
-    } else {
-        const double* u = in.rr ? (in.mode == WRNN_MODE_MOL ? R.rot_rrm : in.cpw > 16 ? R.rot_rr10 : R.rot_rr9)
-                                : (in.mode == WRNN_MODE_MOL ? R.rot_genm : R.rot_gen);
-        t_hi = u[nr];
-        t_lo = u[nr - 1];
-    }
-    if (in.rot_hi > 0 && in.rot_lo > 0) {
-        t_hi = in.rot_hi;
-        t_lo = in.rot_lo;
-    }
-    // (the MOL 3-row rotated instance keeps one spilled register: tolerated, §3.0e)
-    const int rs = in.scr_rot[out.sparse ? 1 : 0][nr];
-    if (rs < 0 || rs > 8) return;
-    if (plan_rotation(B, S, t_hi, t_lo, out.rot, R.rot[0], R.rot[1])) {
-        out.lplan.clear();
-        for (int j = 0; j < out.rot.K; ++j) out.lplan.push_back({0, nr, false, j});
-    }
-}
-
-// The per-step streams a planned call writes before its launches, and whether the workspace check
-// admits the persistent engine. One function for generate_impl (which sets p1_stream / gen_ring
-// from it), wrnn_stream_info and wrnn_debug_stream_bytes, so the three cannot drift.
-//   P1:    [S][Bp][np] floats unless every launch forms P1 in-kernel (fatchord ring, runtimeracer
-//          and geneing calls of wide launches only); then step 0 alone is formed: 0 bytes
-//   noise: the extent of the [S][Bp][n] Gumbel (RAW) or [S][Bp][kMolNoise] MOL stream; 0 when every
-//          launch draws in-kernel (Beta; RAW calls of in-kernel-noise wide launches only)
-// geneing ring (gen_frames: the per-frame P1 form exists and the ring instances run spill-free):
-// only calls whose launches are all wide, never time-sliced. sw = WRNN_GEN_RING: 1 the ring where
-// possible, 0 the streams, -1 the default -- the ring when the streams would not fit the
-// workspace cap, or when the head's measured call time is not above the stream form's
-// (kGenRingDefault).
-// The cap: fatchord and runtimeracer keep the whole-call bound S Bp (4 H + n) 4 bytes whatever
-// they write; geneing counts the streams the call really writes (P1 with its cI column).
-constexpr bool kGenRingDefault[3] = {true, true, true};  // BITS, MOL, Beta
-struct StreamPlan {
-    double p1_bytes = 0, noise_bytes = 0;
-    bool p1_stream = true, gen_ring = false, persist_ok = false;
-};
-StreamPlan plan_streams(const PlanIn& in, const PlanOut& out, bool p1x4, bool gen_frames, int sw) {
-    StreamPlan sp;
-    const int H = in.fat ? kPH : kRH;
-    const double rows_steps = (double)in.S * out.Bplan;
-    bool any_wide = false, any_reg = false;
-    for (const auto& L : out.lplan) {
-        any_wide |= L.wide;
-        any_reg |= !L.wide;
-    }
-    const bool all_wide = any_wide && !any_reg;
-    const bool raw = in.mode == WRNN_MODE_RAW;
-    sp.p1_stream = !out.p1_ring;
-    if (in.rr && in.rr_frames && all_wide) sp.p1_stream = false;  // runtimeracer: only wide launches
-    const double p1_full = rows_steps * (p1x4 ? 4 : 3) * H * 4.0;
-    const double noise_unit = in.mode == WRNN_MODE_BETA ? 0.0 : raw ? in.n * 4.0 : kMolNoise * 4.0;
-    // (persist_noise: RAW calls of fatchord / runtimeracer wide launches only draw in-kernel)
-    double noise = raw && all_wide && !in.gen ? 0.0 : rows_steps * noise_unit;
-    if (in.gen) {
-        const double cap_p1 = rows_steps * 4 * H * 4.0;  // (P1 and cI: 4 H floats either way)
-        const bool streams_fit = cap_p1 + noise <= kPersistWsBytes;
-        const bool can = gen_frames && all_wide && out.wrot.empty() && in.mode >= 0 && in.mode <= 2;
-        sp.gen_ring = can && sw != 0 && (sw == 1 || !streams_fit || kGenRingDefault[in.mode]);
-        // (a 32-row launch exists only as a ring instance: plan_call offers it only where `can`
-        // holds and the switch is not 0, so its plan always takes the ring)
-        bool any32 = false;
-        for (const auto& L : out.lplan) any32 |= L.wide && L.nr > kPWideRows;
-        if (any32) sp.gen_ring = can && sw != 0;
-        if (sp.gen_ring) {
-            sp.p1_stream = false;
-            if (raw) noise = 0.0;  // (MOL keeps its k_mol_noise stream)
-        }
-        sp.persist_ok = (sp.gen_ring ? 0.0 : cap_p1) + noise <= kPersistWsBytes;
-    } else {
-        sp.persist_ok = rows_steps * (4 * H + in.n) * 4.0 <= kPersistWsBytes;
-    }
-    sp.p1_bytes = sp.p1_stream ? p1_full : 0.0;
-    sp.noise_bytes = noise;
-    return sp;
-}
-
 // PlanIn of a call on this handle: variant scratch from the device code objects, env switches.
 PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
     PlanIn in;
@@ -3251,12 +2623,8 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
         if (!std::strcmp(e, "0")) in.sp = false;
         if (!std::strcmp(e, "1")) in.force_sp = true;
     }
-    in.has_wide = in.fat && W.wwide != nullptr;
-    in.has_wide_rr = W.rr && W.wwide_rr != nullptr && in.mode == WRNN_MODE_RAW;
-    in.has_wide_rr_mol = W.rr && W.wwide_rr != nullptr && in.mode == WRNN_MODE_MOL;
-    in.has_wide_gen = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_RAW;
-    in.has_wide_gen_mol = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_MOL;
-    in.has_wide_gen_beta = W.gen && W.wwide_gen != nullptr && in.mode == WRNN_MODE_BETA;
+    // (the handle's mode is its head: wrnn_create admits Beta for geneing only)
+    in.has_wide = (in.fat ? W.wwide : W.rr ? W.wwide_rr : W.gen ? W.wwide_gen : nullptr) != nullptr;
     if (!W.ok) return in;
     for (int c = 1; c <= kPNR; ++c) {
         if (in.fat) {
@@ -3272,13 +2640,14 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
                                                  : persist_gen_rot_scratch(c, in.mode);
         }
     }
-    if (in.has_wide) {
-        in.wide_scr = persist_wide_scratch(in.c10, in.mode == WRNN_MODE_MOL);
-        in.wide_rot_scr = persist_wide_rot_scratch(in.c10, in.mode == WRNN_MODE_MOL);
-    } else if (in.has_wide_rr || in.has_wide_rr_mol) {
-        in.wide_scr = persist_wide_rr_scratch(in.has_wide_rr_mol);
-        in.wide_rot_scr = persist_wide_rr_rot_scratch(in.has_wide_rr_mol);
-    } else if (in.has_wide_gen || in.has_wide_gen_mol || in.has_wide_gen_beta) {
+    const bool mol = in.mode == WRNN_MODE_MOL;
+    if (in.has_wide && in.fat) {
+        in.wide_scr = persist_wide_scratch(in.c10, mol);
+        in.wide_rot_scr = persist_wide_rot_scratch(in.c10, mol);
+    } else if (in.has_wide && W.rr) {
+        in.wide_scr = persist_wide_rr_scratch(mol);
+        in.wide_rot_scr = persist_wide_rr_rot_scratch(mol);
+    } else if (in.has_wide) {
         in.wide_scr = persist_wide_gen_scratch(in.mode);
     }
     if (const char* e = std::getenv("WRNN_PERSIST_WIDE")) in.wmode = std::atoi(e);
@@ -3405,9 +2774,9 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
             return fail(WRNN_ERR_INVALID, "persist engine unavailable: " + why);
     }
     const int Bp = use_p ? Bplan : B;  // persistent groups carry nr rows per launch
-    h->p_plan = use_p ? lplan : std::vector<wrnn_handle::PLaunch>();
-    h->wrot = use_p ? pout.wrot : std::vector<wrnn_handle::WLaunch>();
-    h->rot_plan = use_p ? pout.rot : wrnn_handle::RotPlan();
+    h->p_plan = use_p ? lplan : std::vector<PLaunch>();
+    h->wrot = use_p ? pout.wrot : std::vector<WLaunch>();
+    h->rot_plan = use_p ? pout.rot : RotPlan();
     // P1: the fatchord launches (register-resident and wide) form it in-kernel when the
     // per-frame form exists; the [S][B][4H] stream is written only for the other kernels
     h->p1_ring = use_p && pout.p1_ring;
@@ -3997,32 +3366,6 @@ int wrnn_debug_beta(uint64_t seed, uint32_t stream, uint32_t step, uint32_t row,
     return WRNN_OK;
 }
 
-int wrnn_debug_rot_plan(int rows, int seq_len, double us_hi, double us_lo, int* launches, int* n_hi,
-                        int* n_lo, int* vmap, size_t capacity) {
-    if (!launches || !n_hi || !n_lo) return fail(WRNN_ERR_INVALID, "null argument");
-    if (rows < 1 || seq_len < 1 || !(us_hi > 0) || !(us_lo > 0)) return fail(WRNN_ERR_INVALID, "bad arguments");
-    wrnn_handle::RotPlan P;
-    *launches = *n_hi = *n_lo = 0;
-    if (!plan_rotation(rows, seq_len, us_hi, us_lo, P)) return WRNN_OK;
-    const int q = rows / kPG, nv = kPG * P.nr_hi;
-    if (vmap) {
-        if (capacity < (size_t)P.K * nv * 2) return fail(WRNN_ERR_CAPACITY, "capacity");
-        for (int j = 0; j < P.K; ++j)
-            for (int v = 0; v < nv; ++v) {
-                const int g = v % kPG, r = v / kPG;
-                const bool used = r < P.gnr[(size_t)j * kPG + g];
-                const int2 m = P.vmap[(size_t)j * nv + v];
-                vmap[((size_t)j * nv + v) * 2] = used ? m.x : -1;
-                vmap[((size_t)j * nv + v) * 2 + 1] = used ? m.y : -1;
-            }
-    }
-    (void)q;
-    *launches = P.K;
-    *n_hi = P.n_hi;
-    *n_lo = P.n_lo;
-    return WRNN_OK;
-}
-
 int wrnn_set_rates(wrnn_handle* h, const char* table) {
     if (!h) return fail(WRNN_ERR_INVALID, "null handle");
     if (!table) {
@@ -4045,83 +3388,6 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap) {
     return WRNN_OK;
 }
 
-constexpr int kPlanRowsMax = 1 << 20;  // wrnn_debug_plan: far above any call (C4 is 144 rows per GPU)
-// PlanIn of a described call (wrnn_debug_plan, wrnn_debug_stream_bytes): every variant spill-free
-static int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_len, int flags, PlanIn& in) {
-    if (rows < 1 || seq_len < 1) return fail(WRNN_ERR_INVALID, "bad arguments");
-    // (1 << bits below; the planner's tables have rows + 1 entries)
-    if (bits < 1 || bits > 10) return fail(WRNN_ERR_INVALID, "bits must be 1..10");
-    if (mode != WRNN_MODE_RAW && mode != WRNN_MODE_MOL && mode != WRNN_MODE_BETA)
-        return fail(WRNN_ERR_INVALID, "mode must be one of WRNN_MODE_*");
-    if (rows > kPlanRowsMax) return fail(WRNN_ERR_INVALID, "rows above " + std::to_string(kPlanRowsMax));
-    in = PlanIn();
-    in.ok = true;
-    in.fat = model_type == WRNN_MODEL_FATCHORD;
-    in.rr = model_type == WRNN_MODEL_RUNTIMERACER;
-    in.gen = model_type == WRNN_MODEL_GENEING;
-    if (!in.fat && !in.rr && !in.gen) return fail(WRNN_ERR_INVALID, "model type");
-    in.mode = mode;
-    in.n = mode == WRNN_MODE_RAW ? (1 << bits) : mode == WRNN_MODE_BETA ? 2 : 30;
-    in.cpw = (in.n + kPM - 1) / kPM;  // (classes per slot, as pack_persist* sets it)
-    in.c10 = in.n > kPM * 16;
-    in.B = rows;
-    in.S = seq_len;
-    // flags: 1 sparse image, 2 P1 ring / per-frame P1 (fatchord, runtimeracer), 4 wide images
-    // (fatchord RAW / MOL, runtimeracer RAW, geneing BITS with 512 or 1024 classes), 16 the
-    // runtimeracer MOL wide image, 32 the geneing MOL wide image, 64 the geneing Beta wide image;
-    // every variant spill-free. (128, geneing in-kernel conditioning, enters the plan only through
-    // 256: the geneing 32-row ring instances are available and selected -- it needs 128 and the
-    // head's flag 4 / 32 / 64; wrnn_debug_stream_bytes)
-    in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
-    in.force_sp = in.sp && (flags & 8);
-    in.p1ring = in.fat && (flags & 2);
-    in.rr_frames = in.rr && (flags & 2);
-    in.has_wide = in.fat && (flags & 4) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
-    in.has_wide_rr = in.rr && (flags & 4) && mode == WRNN_MODE_RAW;
-    in.has_wide_rr_mol = in.rr && (flags & 16) && mode == WRNN_MODE_MOL;
-    in.has_wide_gen = in.gen && (flags & 4) && mode == WRNN_MODE_RAW && (in.n == 512 || in.n == 1024);
-    in.has_wide_gen_mol = in.gen && (flags & 32) && mode == WRNN_MODE_MOL;
-    in.has_wide_gen_beta = in.gen && (flags & 64) && mode == WRNN_MODE_BETA;
-    in.gen32 = (flags & 256) && (flags & 128) && (in.has_wide_gen || in.has_wide_gen_mol || in.has_wide_gen_beta);
-    for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
-    return WRNN_OK;
-}
-
-int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
-                    int* n_launches, int* rows_per_group, int* wide, int cap, int* rot_launches) {
-    if (!n_launches || !rot_launches) return fail(WRNN_ERR_INVALID, "null argument");
-    if (cap < 0) return fail(WRNN_ERR_INVALID, "bad arguments");
-    PlanRates R;
-    std::string err;
-    PlanIn in;
-    CHECK(debug_plan_in(model_type, bits, mode, rows, seq_len, flags, in));
-    if (table && !parse_rates(table, R, err)) return fail(WRNN_ERR_INVALID, "rate table: " + err);
-    PlanOut out;
-    plan_call(in, R, out);
-    *n_launches = (int)out.lplan.size();
-    *rot_launches = out.rot.K;
-    for (int i = 0; i < (int)out.lplan.size() && i < cap; ++i) {
-        if (rows_per_group) rows_per_group[i] = out.lplan[i].nr;
-        if (wide) wide[i] = out.lplan[i].wide ? 1 : 0;
-    }
-    return WRNN_OK;
-}
-
-int wrnn_debug_stream_bytes(int model_type, int bits, int mode, int rows, int seq_len, int flags,
-                            double* p1_bytes, double* noise_bytes, int* persist_ok) {
-    if (!p1_bytes || !noise_bytes || !persist_ok) return fail(WRNN_ERR_INVALID, "null argument");
-    PlanIn in;
-    CHECK(debug_plan_in(model_type, bits, mode, rows, seq_len, flags, in));
-    PlanOut out;
-    plan_call(in, PlanRates(), out);  // the shipped rates
-    // (the x4 P1 form of the shipped models; no switch: the default rule)
-    const StreamPlan sp = plan_streams(in, out, true, in.gen && (flags & 128), -1);
-    *p1_bytes = sp.p1_bytes;
-    *noise_bytes = sp.noise_bytes;
-    *persist_ok = !out.lplan.empty() && sp.persist_ok ? 1 : 0;
-    return WRNN_OK;
-}
-
 int wrnn_stream_info(wrnn_handle* h, uint64_t* p1_bytes, uint64_t* noise_bytes) {
     if (!h || !p1_bytes || !noise_bytes) return fail(WRNN_ERR_INVALID, "null argument");
     *p1_bytes = (uint64_t)h->last_p1_bytes;
@@ -4135,29 +3401,6 @@ int wrnn_persist_steps(wrnn_handle* h, int stage, double* steps_per_launch) {
         return fail(WRNN_ERR_INVALID, "bad stage index");
     const auto& q = h->pstages[stage];
     *steps_per_launch = q.launches ? q.steps / q.launches : 0.0;
-    return WRNN_OK;
-}
-
-int wrnn_debug_slice_plan(int rows, int seq_len, int* launches, int* rows_steps, size_t rs_capacity, int* vmap,
-                          size_t capacity) {
-    if (!launches || !rows_steps) return fail(WRNN_ERR_INVALID, "null argument");
-    if (rows < 1 || seq_len < 1) return fail(WRNN_ERR_INVALID, "bad arguments");
-    std::vector<wrnn_handle::WLaunch> sl;
-    *launches = 0;
-    if (!plan_wide_slices(rows, seq_len, sl)) return WRNN_OK;
-    const int K = (int)sl.size(), nv = kPG * kPWideRows;
-    if (rs_capacity < 2 * (size_t)K || (vmap && capacity < (size_t)K * nv * 2)) return fail(WRNN_ERR_CAPACITY, "capacity");
-    for (int k = 0; k < K; ++k) {
-        rows_steps[2 * k] = sl[k].nr;
-        rows_steps[2 * k + 1] = sl[k].steps;
-        if (vmap)
-            for (int v = 0; v < nv; ++v) {
-                const bool used = v < kPG * sl[k].nr;
-                vmap[((size_t)k * nv + v) * 2] = used ? sl[k].vmap[v].x : -1;
-                vmap[((size_t)k * nv + v) * 2 + 1] = used ? sl[k].vmap[v].y : -1;
-            }
-    }
-    *launches = K;
     return WRNN_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan_consts.h"  // kPG, kPM, kPNR, kPH, kRH, kPWideRows, kPWideGen32Rows, kMolNoise
+
 namespace wrnn {
 
 constexpr int kThreads = 256;  // every kernel: 4 wave64 per workgroup
@@ -166,11 +168,7 @@ hipError_t launch_p1_expand(float* P1, int Btot, int row0, int Bu, int f0, int S
 // host pads the row count to a multiple of 8*NR and runs one launch per row batch when the
 // rows exceed what one launch holds register-resident.
 // ---------------------------------------------------------------------------------------
-constexpr int kPG = 8;       // groups (one per XCD)
-constexpr int kPM = 32;      // workgroups per group
 constexpr int kPT = 512;     // threads per workgroup
-constexpr int kPNR = 4;      // max fold rows per group -> B <= 32
-constexpr int kPH = 512;     // rnn_dims == fc_dims
 constexpr int kPK4 = kPH / 4;
 constexpr int kPCls = 32;    // max classes per workgroup -> n_classes <= 1024
 constexpr int kPPhases = 32; // diagnostic stamps per workgroup per traced step
@@ -262,7 +260,6 @@ struct PersistArgs {
 hipError_t launch_persist(const PersistArgs& a, hipStream_t s);
 // Wide-row fatchord launch: up to kPWideRows rows per XCD group (8 kPWideRows per launch),
 // fp32 MFMA products, RAW categorical with <= 1024 classes (> 512: PersistArgs::wfc3b).
-constexpr int kPWideRows = 16;
 hipError_t launch_persist_wide(const PersistArgs& a, hipStream_t s);
 size_t persist_wide_lds_bytes();
 size_t persist_wide_xbuf_floats();
@@ -275,14 +272,12 @@ int persist_wide_rot_scratch(bool c10 = false, bool mol = false);  // the time-s
 int wide_layout_check(int rows_per_group);  // host: violations of the exchange layout (wide_layout.h)
 int wide_mol_layout_check(int rows_per_group);  // host: violations of the MOL logit-pair layout
 hipError_t launch_persist_init(const PersistArgs& a, hipStream_t s);
-constexpr int kMolNoise = 12;  // floats per (step, row) of the precomputed MOL noise
 // ---------------------------------------------------------------------------------------
 // Persistent runtimeracer recurrence (kernels_persist_rr.hip): rnn_dims = fc_dims = 256, four
 // GRUs and five linears per step. Same 8 XCD-local groups x 32 workgroups x 512 threads; a
 // workgroup owns 8 units / outputs of every layer and cpw classes of fc5; eight in-group hops
 // per step (GRU2, GRU3, GRU4, fc1, fc2, fc3, fc4, fc5 candidates).
 // ---------------------------------------------------------------------------------------
-constexpr int kRH = 256;     // rnn_dims == fc_dims
 constexpr int kRNR = 4;      // max fold rows per group and launch
 constexpr int kRNW = 28;     // float4 weight registers per thread
 constexpr int kRRState = 14; // chunk-state floats per row / H: x1, h1, h2, h3, h4 | gh2, gh3, gh4
@@ -430,7 +425,6 @@ int wide_gen_mol_layout_check(int rows_per_group, int n_logits);
 // 32-row ring instances of the wide kernel (k_persist_wide_gen32): up to kPWideGen32Rows rows per
 // XCD group as two MFMA column tiles, ring form only; each tile has its own copy of the group's
 // exchange area, so the xbuf and its reset are twice the 16-row kernel's
-constexpr int kPWideGen32Rows = 32;
 hipError_t launch_persist_wide_gen32_ring(const PersistGenRingArgs& a, hipStream_t s);
 size_t persist_wide_gen32_lds_bytes();
 size_t persist_wide_gen32_xbuf_floats();

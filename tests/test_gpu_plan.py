@@ -1,5 +1,5 @@
-"""Launch plan of the persistent engine (runtime.hip generate_impl: cost-minimising sequence of
-register-resident and wide launches) on the BASELINE shapes, read back through wrnn_plan_info.
+"""Launch plan of the persistent engine (plan.cpp plan_call, on the inputs runtime.hip plan_inputs reads from
+the handle and the device: cost-minimising sequence of register-resident and wide launches) on the BASELINE shapes, read back through wrnn_plan_info.
 
 A regression here costs throughput, not correctness, so the parity tests would not notice it:
 in round 2 the runtimeracer / geneing plan took 4 rows per group for 18 rows (one launch,

@@ -1,4 +1,4 @@
-"""Launch planner rates (runtime.hip plan_call): host only, through
+"""Launch planner rates (plan.cpp plan_call): host only, through
 wrnn_debug_plan (the plan wrnn_generate makes, every variant spill-free) and a rate table.
 
 The planner minimises the summed per-step cost of its launches under a table of measured rates

@@ -1,4 +1,4 @@
-"""Row rotation of the persistent engine (runtime.hip plan_rotation), host
+"""Row rotation of the persistent engine (plan.cpp plan_rotation), host
 planner only: wrnn_debug_rot_plan without a device.
 
 For R fold rows on the 8 XCD groups (q = R // 8, m = R % 8 groups of q + 1 rows), the plan's K

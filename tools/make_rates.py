@@ -5,7 +5,7 @@ Usage: python tools/make_rates.py OUT.txt DIR [DIR ...]
 Reads the bench JSON lines of the probes tools/measure_r06.sh writes (each at a forced rows per
 group, WRNN_PERSIST_NR_MAX=k and no rotation / slicing, so `us_per_step` is that variant's step
 time) and writes `key v1 .. v4` lines for the keys it found; the runtime
-(runtime.hip load_rates) overrides those keys of its built-in defaults and keeps the rest:
+(plan.cpp load_rates) overrides those keys of its built-in defaults and keeps the rest:
   <dir>/nr<k>.log      -> fat9      (fatchord 9-bit, C2 shape)
   <dir>/u10_nr<k>.log  -> fat10     (fatchord 10-bit, its 3000 / 1500 default)
   <dir>/sp_nr<k>.log   -> fat9_sp   (sparse instances, 90 %-pruned weights)
