@@ -218,6 +218,17 @@ int wrnn_fallback_info(wrnn_handle* h, int* count, char* reason, size_t reason_c
  * fullest slot's list size (float4). Results equal the dense kernels' bit for bit. Env
  * WRNN_SPARSE=0 turns it off. Any pointer may be null. */
 int wrnn_sparse_info(wrnn_handle* h, int* available, int* last_call, double* density, int* fill_f4);
+/* The same for wide row batches (the wide form): *available = the loaded fatchord
+ * RAW weights (512 or 1024 classes) have a block-sparse wide image (every slot's live 1 x 4 blocks
+ * fit the kernel's LDS lists; dense or 50 %-pruned weights have none and run dense); *last_call = a
+ * launch of the last call ran the block-sparse wide kernel (stage name persist_wide_sp);
+ * *density = live fraction of the packed step matrices' 1 x 4 blocks; *fill_f4 = the fullest
+ * slot's blocks. Its labels equal the dense wide kernel's except at near-ties (another summation
+ * order); a row's results do not depend on the group fill or on time slicing. Env
+ * WRNN_SPARSE_WIDE=0|1 (read per call) forbids / forces it for the call's wide launches; unset, the
+ * planner takes the cheaper of the rate keys wide and wide_sp per launch. wrnn_sparse_info and
+ * WRNN_SPARSE keep meaning the register-resident family only. Any pointer may be null. */
+int wrnn_sparse_wide_info(wrnn_handle* h, int* available, int* last_call, double* density, int* fill_f4);
 /* Launch-planner rates (operator tuning; no reference equivalent): the per-step
  * costs the planner minimises, as text lines `key v1 v2 ...` ('#' comments; keys and meaning in
  * DESIGN.md). A handle starts from the built-in measured defaults overridden by env WRNN_RATES
@@ -237,9 +248,11 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap);
  * wide_gen_beta, likewise only for calls of more than 32 rows), 256 the geneing 32-row ring instances
  * are available and selected (wrnn_set_gen_wide_rows(32); needs flag 128 of wrnn_debug_stream_bytes
  * and the head's flag 4 / 32 / 64; rate keys wide_gen32, wide_gen32_mol, wide_gen32_beta; only in
- * plans whose launches are all wide). bits outside 1..10, an unknown mode or more than 2^20 rows are
- * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag of the first `cap`,
- * and the row rotation's launch count (0: none). */
+ * plans whose launches are all wide), 512 the block-sparse wide image exists (fatchord RAW, with
+ * flag 4; rate key wide_sp: a wide launch whose wide_sp price is strictly below its wide price is
+ * planned block-sparse). bits outside 1..10, an unknown mode or more than 2^20 rows are
+ * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag (1 the wide MFMA kernel, 2 a
+ * block-sparse wide launch) of the first `cap`, and the row rotation's launch count (0: none). */
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
                     int* n_launches, int* rows_per_group, int* wide, int cap, int* rot_launches);
 /* Launch plan of the last PERSIST call (operator introspection; no reference equivalent):
@@ -335,6 +348,23 @@ int wrnn_rot_info(wrnn_handle* h, int* launches, int* n_hi, int* n_lo);
  * last persistent call: the call's S for row batches, less for rotated / time-sliced launches
  * (DESIGN.md §3.0e-f). */
 int wrnn_persist_steps(wrnn_handle* h, int stage, double* steps_per_launch);
+
+/* Block-sparse wide image of a pruned fatchord model (csrc/sparse_wide_pack.h),
+ * without a device. wrnn_debug_wide_sp_pack: the lists of slot `slot` (0..31) of one row-major
+ * matrix W (rows x cols; rows 512, 1024 or 1536, cols a multiple of 4 up to 512): the slot's
+ * output rows are k * 512 + 16 slot + i, i < 16, for every k < rows / 512, in that order. Writes
+ * their densified reconstruction to recon ([16 rows / 512][cols]), each row's live 1 x 4 blocks to
+ * sizes ([16 rows / 512]) and the slot's blocks to *total_f4; each may be NULL. A block is dead
+ * only if its four words are +0.0 or -0.0. */
+int wrnn_debug_wide_sp_pack(const float* W, int rows, int cols, int slot, float* recon, int* sizes, int* total_f4);
+/* The fit rule over the six step matrices (rnn2.weight_ih_l0 (1536, ld_ih2), rnn1.weight_hh_l0 and
+ * rnn2.weight_hh_l0 (1536, 512), fc1.weight (512, ld_fc1), fc2.weight (512, ld_fc2), fc3.weight
+ * (n_classes, 512); the first 512 columns of each are packed): *fits = every slot's lists fit the
+ * kernel's LDS carve (0: no image, the weights run dense), *density = live fraction of the packed
+ * 1 x 4 blocks, *fill_f4 = the fullest slot's blocks. Outputs may be NULL. */
+int wrnn_debug_wide_sp_image(const float* wih2, int ld_ih2, const float* whh1, const float* whh2, const float* fc1,
+                             int ld_fc1, const float* fc2, int ld_fc2, const float* fc3, int n_classes, int* fits,
+                             double* density, int* fill_f4);
 
 /* Host-side exhaustive check of the wide launch's exchange layout (kernels_persist_wide.hip,
  * csrc/wide_layout.h) for a group of `rows_per_group` rows (1..16): returns the number of

@@ -48,8 +48,7 @@ using wide::WSLOT;
 using wide::WV;
 using wide::WX_D;
 using wide::WX_GROUP;
-enum WBuf : int { WB_X1 = 0, WB_H1, WB_X2, WB_H2, WB_Y1, WB_Y2, WB_N };
-static_assert(WB_N == wide::kBufs, "one slot pair per published vector");
+// (enum WBuf, the published vectors: persist_wide_common.h)
 // ---- LDS (floats) -------------------------------------------------------------------------
 // Everything read per step sits in the first 64 KiB so every ds_read / ds_write offset fits
 // the instruction's 16-bit immediate (beyond it each access would pin an address register).
@@ -81,68 +80,7 @@ __device__ __forceinline__ float bop(const u4v (&cc)[4], int ks) {
 }
 // (mfma4, f4c, the partial tiles' swizzle wsw, packet_ready and lds_barrier: persist_wide_common.h)
 
-// Poll this lane's 4 packets of one hop buffer slot (byte offset of packet 0: voff; packet p at
-// voff + 1 KiB p; so: the buffer and slot) until no value is the sentinel, all 4 in flight on
-// every pass. Lanes with valid == false (rows beyond the group's count) contribute zeros.
-// Why a sentinel is enough (no step tags): a producer writes step s into slot s & 1 and the
-// sentinel into slot (s + 1) & 1 (pub). Its next poll waits for every older vector memory
-// operation of the wave (vmcnt counts stores on gfx9), so that reset is in L2 before it
-// publishes anything later; a consumer polls slot (s + 1) & 1 for step s + 1 only after it has
-// read such a later publication, so it sees the reset or the new value, never step s - 1. And
-// slot s & 1 is rewritten (step s + 2) only after every consumer has published past its reads
-// of step s.
-// The 4 packet loads of a poll round. Unconditional: a lane without an operand loads from an
-// out-of-range offset, which reads 0 ("ready"), so every path carries the same loads and the
-// compiler's waits stay counted (a branch around them made the waits after it conservative).
-// w_issue alone: the first round issued early, for an off-path operand published long before
-// its use, checked later by w_poll with pre = true.
-__device__ __forceinline__ void w_issue(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v (&cc)[4]) {
-    unsigned vo = valid ? voff : wide::kNoOffset;
-    asm volatile("" : "+v"(vo));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cc[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024u * i, so, kCpNT);
-}
-// Packet i of a poll round alone (see w_issue): issued into a packet register an off-path
-// product has finished reading, so a critical hop's first round needs no extra registers.
-__device__ __forceinline__ void w_issue1(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v& c, int i) {
-    unsigned vo = valid ? voff : wide::kNoOffset;
-    asm volatile("" : "+v"(vo));
-    c = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024u * i, so, kCpNT);
-}
-// On a timeout the first poller records its site, whether its packets were missing and the step
-// (spin_give_up).
-__device__ __forceinline__ bool w_poll(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v (&cc)[4],
-                                       unsigned* ctl, unsigned where, unsigned step, bool pre = false) {
-    const unsigned t0 = p_now();
-    unsigned nsp = 0;
-    if (!pre) w_issue(xr, voff, so, valid, cc);
-    {
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ok &= packet_ready(cc[i]);
-        if (__all(ok)) return true;
-    }
-    while (true) {
-        // every packet reloaded per spin: a lane's 4 packets come from one producer slot's one
-        // store instruction, so when packet 0 lands the others have too and no second L2 round
-        // trip follows (round 3 A/B: 11.33 against 11.48 us per step spinning on packet 0,
-        // profiles/r03/ab_spin/)
-        w_issue(xr, voff, so, valid, cc);
-        {
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ok &= packet_ready(cc[i]);
-            if (__all(ok)) return true;
-        }
-        if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
-            bool mok = true;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) mok &= packet_ready(cc[i]);
-            spin_give_up(ctl, where, step, !__all(mok));
-            return false;
-        }
-    }
-}
+// (w_issue, w_issue1 and w_poll, the polls of a hop's 4 packets: persist_wide_common.h)
 
 // DBG: the instance that records logits for the teacher-forced gate (wrnn_set_debug_steps)
 // ROT: a time-sliced launch (PersistArgs::vmap): row slot r of group g is the
@@ -937,31 +875,37 @@ int wide_mol_layout_check(int R) {
     return bad;
 }
 
-int persist_wide_scratch(bool c10, bool mol) {
+int persist_fn_scratch(const void* f) {
     hipFuncAttributes fa;
-    const void* f = mol   ? (const void*)k_persist_wide<false, false, true, false>
-                    : c10 ? (const void*)k_persist_wide<false, true, false, false>
-                          : (const void*)k_persist_wide<false, false, false, false>;
-    if (hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
-    return (int)fa.localSizeBytes;
-}
-int persist_wide_rot_scratch(bool c10, bool mol) {
-    hipFuncAttributes fa;
-    const void* f = mol   ? (const void*)k_persist_wide<true, false, true, false>
-                    : c10 ? (const void*)k_persist_wide<true, true, false, false>
-                          : (const void*)k_persist_wide<true, false, false, false>;
     if (hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
     return (int)fa.localSizeBytes;
 }
 
-hipError_t launch_persist_wide(const PersistArgs& a, hipStream_t s) {
+int persist_wide_scratch(bool c10, bool mol) {
+    const void* f = mol   ? (const void*)k_persist_wide<false, false, true, false>
+                    : c10 ? (const void*)k_persist_wide<false, true, false, false>
+                          : (const void*)k_persist_wide<false, false, false, false>;
+    return persist_fn_scratch(f);
+}
+int persist_wide_rot_scratch(bool c10, bool mol) {
+    const void* f = mol   ? (const void*)k_persist_wide<true, false, true, false>
+                    : c10 ? (const void*)k_persist_wide<true, true, false, false>
+                          : (const void*)k_persist_wide<true, false, false, false>;
+    return persist_fn_scratch(f);
+}
+
+bool persist_wide_args_ok(const PersistArgs& a) {
     if (a.rb < 0 || a.nr < 1 || a.nr > kPWideRows || a.rb + kPG * a.nr > a.B || a.n_classes > 2 * kPM * 16 ||
-        (a.mode != 0 && a.mode != 1) || a.wwide == nullptr ||
-        (a.n_classes > kPM * 16 && a.wfc3b == nullptr))
+        (a.mode != 0 && a.mode != 1))
+        return false;
+    return !(a.vmap && a.p1q == nullptr);  // time-sliced rows: P1 formed in-kernel
+}
+
+hipError_t launch_persist_wide(const PersistArgs& a, hipStream_t s) {
+    if (!persist_wide_args_ok(a) || a.wwide == nullptr || (a.n_classes > kPM * 16 && a.wfc3b == nullptr))
         return hipErrorInvalidValue;
     const size_t lb = persist_wide_lds_bytes();
     const bool dbg = a.dbg.out != nullptr;
-    if (a.vmap && a.p1q == nullptr) return hipErrorInvalidValue;  // time-sliced rows: P1 formed in-kernel
     if (a.mode == 1) {  // MOL
         // 30 logits in slots 0 and 1; the draws come from the k_mol_noise stream, indexed in 32 bits
         if (a.n_classes != wide::kMolLogits || a.gumbel == nullptr ||

@@ -61,6 +61,74 @@ __device__ __forceinline__ void spin_give_up(unsigned* ctl, unsigned where, unsi
     }
 }
 
+// The vectors a step of the fatchord wide kernels publishes (kernels_persist_wide.hip,
+// kernels_persist_wide_sp.hip): one slot pair each in the exchange area (wide_layout.h)
+enum WBuf : int { WB_X1 = 0, WB_H1, WB_X2, WB_H2, WB_Y1, WB_Y2, WB_N };
+static_assert(WB_N == wide::kBufs, "one slot pair per published vector");
+
+// Poll this lane's 4 packets of one hop buffer slot (byte offset of packet 0: voff; packet p at
+// voff + 1 KiB p; so: the buffer and slot) until no value is the sentinel, all 4 in flight on
+// every pass. Lanes with valid == false (rows beyond the group's count) contribute zeros.
+// Why a sentinel is enough (no step tags): a producer writes step s into slot s & 1 and the
+// sentinel into slot (s + 1) & 1 (pub). Its next poll waits for every older vector memory
+// operation of the wave (vmcnt counts stores on gfx9), so that reset is in L2 before it
+// publishes anything later; a consumer polls slot (s + 1) & 1 for step s + 1 only after it has
+// read such a later publication, so it sees the reset or the new value, never step s - 1. And
+// slot s & 1 is rewritten (step s + 2) only after every consumer has published past its reads
+// of step s.
+// The 4 packet loads of a poll round. Unconditional: a lane without an operand loads from an
+// out-of-range offset, which reads 0 ("ready"), so every path carries the same loads and the
+// compiler's waits stay counted (a branch around them made the waits after it conservative).
+// w_issue alone: the first round issued early, for an off-path operand published long before
+// its use, checked later by w_poll with pre = true.
+__device__ __forceinline__ void w_issue(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v (&cc)[4]) {
+    unsigned vo = valid ? voff : wide::kNoOffset;
+    asm volatile("" : "+v"(vo));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cc[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024u * i, so, kCpNT);
+}
+// Packet i of a poll round alone (see w_issue): issued into a packet register an off-path
+// product has finished reading, so a critical hop's first round needs no extra registers.
+__device__ __forceinline__ void w_issue1(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v& c, int i) {
+    unsigned vo = valid ? voff : wide::kNoOffset;
+    asm volatile("" : "+v"(vo));
+    c = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024u * i, so, kCpNT);
+}
+// On a timeout the first poller records its site, whether its packets were missing and the step
+// (spin_give_up).
+__device__ __forceinline__ bool w_poll(rsrc_t xr, unsigned voff, unsigned so, bool valid, u4v (&cc)[4],
+                                       unsigned* ctl, unsigned where, unsigned step, bool pre = false) {
+    const unsigned t0 = p_now();
+    unsigned nsp = 0;
+    if (!pre) w_issue(xr, voff, so, valid, cc);
+    {
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ok &= packet_ready(cc[i]);
+        if (__all(ok)) return true;
+    }
+    while (true) {
+        // every packet reloaded per spin: a lane's 4 packets come from one producer slot's one
+        // store instruction, so when packet 0 lands the others have too and no second L2 round
+        // trip follows (round 3 A/B: 11.33 against 11.48 us per step spinning on packet 0,
+        // profiles/r03/ab_spin/)
+        w_issue(xr, voff, so, valid, cc);
+        {
+            bool ok = true;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ok &= packet_ready(cc[i]);
+            if (__all(ok)) return true;
+        }
+        if ((++nsp & 63) == 0 && (ld_sc1_u(ctl + PC_ERR) || p_now() - t0 > kSpinTicks)) {
+            bool mok = true;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mok &= packet_ready(cc[i]);
+            spin_give_up(ctl, where, step, !__all(mok));
+            return false;
+        }
+    }
+}
+
 // Sample hop of the MOL / Beta heads: lane (row, cul) polls the tagged pairs (float bits, the
 // whole step tag seq) of logits cul (at byte offset va, wanted where ra) and 16 + cul (vb, rb) of
 // its row in the area at scalar offset so; a lane without a logit passes kNoOff (reads 0, not

@@ -38,6 +38,7 @@ const RateKey kRateKeys[] = {
     {"rr", RATE_AT(R.rr + 1), kPNR},
     {"gen", RATE_AT(R.gen + 1), kPNR},
     {"wide", RATE_AT(R.wide), 3},
+    {"wide_sp", RATE_AT(R.wide_sp), 3},
     {"wide_mol", RATE_AT(R.wide_mol), 2},
     {"wide_rr", RATE_AT(R.wide_rr), 2},
     {"wide_rr_mol", RATE_AT(R.wide_rr_mol), 2},
@@ -287,6 +288,12 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
         const double* k = hd->key(R);
         return k[0] + k[1] * r + (hd->c10_term && in.c10 ? k[2] : 0.0);
     };
+    // fatchord RAW with the block-sparse wide image: a wide launch of r rows per group runs sparse
+    // when forced or when its key is strictly cheaper, and is priced with the one it runs
+    const bool sp_head = hd && in.fat && in.mode == WRNN_MODE_RAW && in.has_wide_sp && in.sp_wide_mode != 0;
+    auto wide_sp_us = [&](int r) { return R.wide_sp[0] + R.wide_sp[1] * r + (in.c10 ? R.wide_sp[2] : 0.0); };
+    auto wide_is_sp = [&](int r) { return sp_head && (in.sp_wide_mode == 1 || wide_sp_us(r) < wide_us(r)); };
+    auto wide_cost = [&](int r) { return wide_is_sp(r) ? wide_sp_us(r) : wide_us(r); };
     // a wide MOL launch indexes the k_mol_noise stream ([S][rows][kMolNoise], rows padded to a
     // launch) in 32 bits: it must stay below 2 GiB (launch_persist_wide and
     // launch_persist_wide_rr refuse it otherwise)
@@ -335,7 +342,7 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
                                   ((in.wide_scr >= 0 && in.wide_scr <= hd->max_scratch) || in.allow_wide_scratch);
         if (wide_offered) {
             if (in.wmode == 1) opts.clear();
-            for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, wide_us(r)});
+            for (int r = 1; r <= kPWideRows; ++r) opts.push_back({r, true, wide_cost(r)});
         }
         if (in.nr_max > 0) {  // diagnostic: variant A/B (WRNN_PERSIST_NR_MAX)
             const int c = std::max(1, std::min(kPNR, in.nr_max));
@@ -394,7 +401,7 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
         std::vector<WLaunch> sl;
         if (plan_wide_slices(B, S, sl)) {
             double cost = R.slice[0] * (sl.size() - 1);  // (an extra launch: weights, ring prologue)
-            for (const auto& L : sl) cost += L.steps * wide_us(L.nr);
+            for (const auto& L : sl) cost += L.steps * wide_cost(L.nr);
             if (cost < R.slice[1] * out.plan_us * S) {
                 out.lplan.clear();
                 for (int j = 0; j < (int)sl.size(); ++j) out.lplan.push_back({0, sl[j].nr, true, j});
@@ -402,6 +409,7 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
             }
         }
     }
+    for (auto& L : out.lplan) L.sp = L.wide && wide_is_sp(L.nr);
     const auto& lp = out.lplan;
     out.Bplan = lp.empty() ? B : !out.wrot.empty() ? B : lp.back().rb + kPG * lp.back().nr;
     // P1 ring (fatchord): on unless a register-resident launch spills more with it than with the
@@ -525,7 +533,8 @@ int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_len, int
     // runtimeracer MOL wide image, 32 the geneing MOL wide image, 64 the geneing Beta wide image;
     // every variant spill-free. (128, geneing in-kernel conditioning, enters the plan only through
     // 256: the geneing 32-row ring instances are available and selected -- it needs 128 and the
-    // head's flag 4 / 32 / 64; wrnn_debug_stream_bytes)
+    // head's flag 4 / 32 / 64; wrnn_debug_stream_bytes); 512 the block-sparse wide image (fatchord
+    // RAW, with flag 4)
     in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.force_sp = in.sp && (flags & 8);
     in.p1ring = in.fat && (flags & 2);
@@ -535,6 +544,7 @@ int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_len, int
                           : in.rr ? (raw ? 4 : mol ? 16 : 0)
                                   : (raw ? (in.n == 512 || in.n == 1024 ? 4 : 0) : mol ? 32 : 64);
     in.has_wide = (flags & head_flag) != 0;
+    in.has_wide_sp = (flags & 512) && in.fat && raw && in.has_wide;
     in.gen32 = (flags & 256) && (flags & 128) && in.gen && in.has_wide;
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
     return WRNN_OK;
@@ -561,7 +571,7 @@ int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int r
     *rot_launches = out.rot.K;
     for (int i = 0; i < (int)out.lplan.size() && i < cap; ++i) {
         if (rows_per_group) rows_per_group[i] = out.lplan[i].nr;
-        if (wide) wide[i] = out.lplan[i].wide ? 1 : 0;
+        if (wide) wide[i] = out.lplan[i].sp ? 2 : out.lplan[i].wide ? 1 : 0;
     }
     return WRNN_OK;
 }

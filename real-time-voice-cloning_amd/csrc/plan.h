@@ -28,6 +28,12 @@ struct PlanRates {
     // 9.72 us at 16 rows (profiles/r05/final/c4.log, r06/b sp_c4), 10.965 at 16 rows / 1024
     // classes (r05/final/b10.log), 10.59 at 6 rows / 1024 classes (r06/b u10_wide)
     double wide[3] = {9.32, 0.025, 1.24};
+    // block-sparse wide launches of a pruned fatchord RAW model (k_persist_wide_sp, §3.0g the wide
+    // form; offered only where the sparse-wide image exists), same three terms: 23.03 / 23.47 / 24.32
+    // us at 5 / 9 / 16 rows per group on 90 %-pruned weights, 24.40 / 24.97 / 26.00 at 1024 classes
+    // (profiles/wide_sp/rates.log; the least-squares form of tools/make_rates.py) -- slower than
+    // the dense wide kernel (9.55 / 9.69 / 9.76), so by rate every launch stays dense
+    double wide_sp[3] = {22.434, 0.1173, 1.518};
     // the MOL head on the wide kernel (fatchord): base + row x r. 9.43 / 9.57 / 9.65 us at 5 / 9 /
     // 16 rows per group (profiles/wide_mol/mol_wide_r*.log, least squares: tools/make_rates.py)
     double wide_mol[2] = {9.366, 0.0185};
@@ -82,6 +88,7 @@ struct PLaunch {
     int rb, nr;  // first row, rows per XCD group (the launch runs rows rb + g + 8 r, r < nr)
     bool wide;   // kernels_persist_wide.hip (MFMA) or the register-resident kernel
     int rot = -1;  // launch j of the call's row rotation (rot_plan), or -1
+    bool sp = false;  // a wide launch priced (and to be run) as block-sparse wide (rate key wide_sp)
 };
 // One entry of a virtual-row map: virtual row g + 8 r of a rotated or time-sliced launch runs
 // physical row `row` from step `off` (the kernels read the uploaded maps as int2)
@@ -115,6 +122,10 @@ struct PlanIn {
     bool c10 = false, sp = false, p1ring = false, rr_frames = false;
     bool force_sp = false;  // env WRNN_SPARSE=1: the sparse instances whatever the rates
     bool has_wide = false;  // the wide image of this call's head (topology and mode) exists
+    // fatchord RAW: the block-sparse wide image exists too (sparse_wide_pack.h: the pruned weights'
+    // lists fit); sp_wide_mode: env WRNN_SPARSE_WIDE, 0 never, 1 every wide launch, -1 by rate
+    bool has_wide_sp = false;
+    int sp_wide_mode = -1;
     // geneing: the head's 32-row ring instances are selected (wrnn_set_gen_wide_rows / env
     // WRNN_GEN_WIDE_ROWS) and can run -- spill-free, and the call can take the ring (the per-frame
     // P1 form exists, WRNN_GEN_RING is not 0): established before a 32-row launch is priced

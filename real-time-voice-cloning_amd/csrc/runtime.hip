@@ -24,6 +24,7 @@
 #include "cand_key.h"
 #include "philox.h"
 #include "plan.h"
+#include "sparse_wide_pack.h"
 #include "wavernn_mi355x.h"
 #include "wrnn_kernels.h"
 
@@ -185,6 +186,7 @@ struct wrnn_handle {
     int gen_wide_rows = kPWideRows;  // wrnn_set_gen_wide_rows: 16, or 32 (the 32-row ring instances)
     double last_p1_bytes = 0, last_noise_bytes = 0;  // the per-step streams of the last call (wrnn_stream_info)
     bool sparse_call = false;  // this call's k_persist launches run the sparse instances
+    bool sparse_wide_call = false;  // a launch of this call ran the block-sparse wide kernel
     PlanRates rates;           // per-step rates of the launch planner (load_rates, §3.0h)
     bool timing = false;
     int phase_step = -1;  // diagnostic (env WRNN_PHASE_STEP): per-phase stamps of one step
@@ -215,6 +217,11 @@ struct wrnn_handle {
         // sparse k_persist image (pruned checkpoints, pack_persist_sparse):
         // per-lane masks / list bases [kPM][kPT] uint4 and the block lists [kPM][kPLdsW4] float4
         bool sp_ok = false;
+        // block-sparse wide image (pack_persist_wide_sp; kernels_persist_wide_sp.hip): null when
+        // the lists do not fit; the live fraction and the fullest slot's blocks either way
+        const float* wsp_img = nullptr;
+        double wsp_density = 0;
+        int wsp_fill = 0;
         const float *swreg = nullptr, *swlds = nullptr;
         double sp_density = 1.0;   // live fraction of the kernel's 1 x 4 weight blocks
         int sp_fill = 0;           // float4 of the fullest slot's lists (of kPSpZero)
@@ -555,6 +562,7 @@ int pack_p1(wrnn_handle* h, bool x4) {
 }
 
 int pack_persist_wide(wrnn_handle* h);
+int pack_persist_wide_sp(wrnn_handle* h);
 int pack_persist_wide_rr(wrnn_handle* h);
 int pack_persist_wide_gen(wrnn_handle* h);
 
@@ -620,6 +628,7 @@ int pack_persist(wrnn_handle* h, int oG2, int oF1, int oF2) {
     CHECK(rc);
     CHECK(pack_p1(h, true));
     CHECK(pack_persist_wide(h));
+    CHECK(pack_persist_wide_sp(h));
     auto dv = [&](const std::string& key) -> const float* {
         if (!h->dvec.count(key)) h->dvec[key] = upload(h, T[key], &rc);
         return h->dvec[key];
@@ -828,6 +837,34 @@ int pack_persist_wide(wrnn_handle* h) {
     P.wwide = upload(h, wr, &rc);
     CHECK(rc);
     P.wwide_lds = upload(h, wl, &rc);
+    CHECK(rc);
+    return WRNN_OK;
+}
+
+// Block-sparse wide image of a pruned fatchord RAW model (sparse_wide_pack.h; §3.0g, the wide
+// form), built where the wide image exists: per slot the lists of its 13 product sets as
+// slot_image lays them out. Weights whose lists do not fit the kernel's LDS carve (50 % density,
+// dense weights) get no image and run dense.
+int pack_persist_wide_sp(wrnn_handle* h) {
+    auto& T = h->host;
+    auto& P = h->pw;
+    P.wsp_img = nullptr;
+    P.wsp_density = 0;
+    P.wsp_fill = 0;
+    const int H = h->H, F = h->F, A = h->A, n = h->n_classes;
+    if (!P.wwide || h->cfg.mode != WRNN_MODE_RAW || (n != kPM * 16 && n != 2 * kPM * 16)) return WRNN_OK;
+    const wsp::StepMatrices m{T["rnn2.weight_ih_l0"].data(), T["rnn1.weight_hh_l0"].data(), T["rnn2.weight_hh_l0"].data(),
+                              T["fc1.weight"].data(), T["fc2.weight"].data(), T["fc3.weight"].data(),
+                              H + A, H, H, H + A, F + A, F, n};
+    const wsp::Image im = wsp::build_image(m);
+    P.wsp_density = im.density();
+    P.wsp_fill = im.fill_f4;
+    if (!im.fits) return WRNN_OK;
+    std::vector<float> img((size_t)kPM * wsp::kImgWords);  // (the words' bits, moved as bytes)
+    for (int w = 0; w < kPM; ++w)
+        wsp::slot_image(im.slots[w], reinterpret_cast<uint32_t*>(img.data()) + (size_t)w * wsp::kImgWords);
+    int rc = WRNN_OK;
+    P.wsp_img = upload(h, img, &rc);
     CHECK(rc);
     return WRNN_OK;
 }
@@ -1928,7 +1965,8 @@ bool persist_device_ok(wrnn_handle* h) {
     bool ok = hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount == kPG * kPM &&
               std::strncmp(p.gcnArchName, "gfx950", 6) == 0 &&
               p.sharedMemPerMultiprocessor >= std::max({persist_lds_bytes(), persist_rr_lds_bytes(),
-                                                        persist_gen_lds_bytes(), persist_wide_lds_bytes()});
+                                                        persist_gen_lds_bytes(), persist_wide_lds_bytes(),
+                                                        persist_wide_sp_lds_bytes()});
     if (d >= 0 && d < 64) cached[d] = ok ? 1 : 2;
     return ok;
 }
@@ -2357,7 +2395,7 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             h->pev.push_back(e0);
             h->pev.push_back(e1);
             h->pev_steps.push_back(steps_b);
-            h->pev_kind.push_back(L.wide ? 1 : 0);
+            h->pev_kind.push_back(L.sp ? 2 : L.wide ? 1 : 0);
             h->pev_rows.push_back(kPG * L.nr);
             HIPC(hipEventRecord(e0, st));
         }
@@ -2416,6 +2454,10 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             } else {
                 le = launch_persist_rr(ar, st);
             }
+        } else if (L.sp) {  // block-sparse wide: the slots' list images in place of the MFMA tiles
+            PersistArgs as = a;
+            as.wwide_lds = (const float4*)W.wsp_img;
+            le = launch_persist_wide_sp(as, st);
         } else if (L.wide) {
             le = launch_persist_wide(a, st);
         } else {
@@ -2543,11 +2585,11 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
             real = B;
             steps = (double)S / h->rot_plan.K;
         }
-        const char* nm = L.wide ? "persist_wide" : "persist";
+        const char* nm = L.sp ? "persist_wide_sp" : L.wide ? "persist_wide" : "persist";
         auto it = std::find_if(h->pstages.begin(), h->pstages.end(),
                                [&](const wrnn_handle::PStage& q) { return q.name == nm; });
         if (it == h->pstages.end()) {
-            h->pstages.push_back({nm, L.wide ? 1 : 0, 0.0, 0});
+            h->pstages.push_back({nm, L.sp ? 2 : L.wide ? 1 : 0, 0.0, 0});
             it = h->pstages.end() - 1;
         }
         it->rows += real;
@@ -2649,6 +2691,15 @@ PlanIn plan_inputs(wrnn_handle* h, int B, int S) {
         in.wide_rot_scr = persist_wide_rr_rot_scratch(mol);
     } else if (in.has_wide) {
         in.wide_scr = persist_wide_gen_scratch(in.mode);
+    }
+    // block-sparse wide launches (§3.0g, the wide form): the image exists and both instances of
+    // the class count run without scratch; env WRNN_SPARSE_WIDE=0|1 (read per call) forbids /
+    // forces them, unset: by the rate keys wide and wide_sp
+    in.has_wide_sp = in.has_wide && in.fat && in.mode == WRNN_MODE_RAW && W.wsp_img != nullptr &&
+                     persist_wide_sp_scratch(false, in.c10) == 0 && persist_wide_sp_scratch(true, in.c10) == 0;
+    if (const char* e = std::getenv("WRNN_SPARSE_WIDE")) {
+        if (!std::strcmp(e, "0")) in.sp_wide_mode = 0;
+        if (!std::strcmp(e, "1")) in.sp_wide_mode = 1;
     }
     if (const char* e = std::getenv("WRNN_PERSIST_WIDE")) in.wmode = std::atoi(e);
     if (const char* e = std::getenv("WRNN_PERSIST_NR_MAX")) in.nr_max = std::atoi(e);
@@ -2781,6 +2832,9 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
     // per-frame form exists; the [S][B][4H] stream is written only for the other kernels
     h->p1_ring = use_p && pout.p1_ring;
     h->sparse_call = use_p && pout.sparse;
+    h->sparse_wide_call = false;
+    if (use_p)
+        for (const auto& L : lplan) h->sparse_wide_call |= L.sp;
     // (the fatchord wide launches form P1 in-kernel too; runtimeracer and geneing: calls of wide
     // launches only -- plan_streams)
     h->p1_stream = use_p && splan.p1_stream;
@@ -3260,6 +3314,15 @@ int wrnn_sparse_info(wrnn_handle* h, int* available, int* last_call, double* den
     if (last_call) *last_call = h->last_engine == WRNN_ENGINE_PERSIST && h->sparse_call ? 1 : 0;
     if (density) *density = h->pw.sp_density;
     if (fill_f4) *fill_f4 = h->pw.sp_fill;
+    return WRNN_OK;
+}
+
+int wrnn_sparse_wide_info(wrnn_handle* h, int* available, int* last_call, double* density, int* fill_f4) {
+    if (!h) return fail(WRNN_ERR_INVALID, "null handle");
+    if (available) *available = h->pw.wsp_img ? 1 : 0;
+    if (last_call) *last_call = h->last_engine == WRNN_ENGINE_PERSIST && h->sparse_wide_call ? 1 : 0;
+    if (density) *density = h->pw.wsp_density;
+    if (fill_f4) *fill_f4 = h->pw.wsp_fill;
     return WRNN_OK;
 }
 

@@ -269,8 +269,19 @@ size_t persist_wide_wreg_floats();
 size_t persist_wide_wlds_floats();
 int persist_wide_scratch(bool c10 = false, bool mol = false);      // (c10: the 1024-class instances; mol: the MOL head's)
 int persist_wide_rot_scratch(bool c10 = false, bool mol = false);  // the time-sliced instance (PersistArgs::vmap)
+// shared by launch_persist_wide and launch_persist_wide_sp: the row range, class count, mode and
+// time-sliced-P1 rule of a wide launch; the scratch bytes of a kernel instance (-1: query error)
+bool persist_wide_args_ok(const PersistArgs& a);
+int persist_fn_scratch(const void* f);
 int wide_layout_check(int rows_per_group);  // host: violations of the exchange layout (wide_layout.h)
 int wide_mol_layout_check(int rows_per_group);  // host: violations of the MOL logit-pair layout
+// Block-sparse wide-row fatchord launch of a pruned model (kernels_persist_wide_sp.hip): RAW, 512
+// or 1024 classes, 1..16 rows per group, on the wide launch's exchange area and reset kernel;
+// PersistArgs::wwide_lds holds the slots' list images ([kPM][wsp::kImgWords] words,
+// sparse_wide_pack.h slot_image).
+hipError_t launch_persist_wide_sp(const PersistArgs& a, hipStream_t s);
+size_t persist_wide_sp_lds_bytes();
+int persist_wide_sp_scratch(bool rot, bool c10);  // scratch bytes of the production instance
 hipError_t launch_persist_init(const PersistArgs& a, hipStream_t s);
 // ---------------------------------------------------------------------------------------
 // Persistent runtimeracer recurrence (kernels_persist_rr.hip): rnn_dims = fc_dims = 256, four

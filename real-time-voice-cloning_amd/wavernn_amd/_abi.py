@@ -43,7 +43,7 @@ EXPORTED = [
     'wrnn_debug_wide_mol_layout', 'wrnn_debug_wide_gen_layout', 'wrnn_debug_wide_rr_mol_layout',
     'wrnn_debug_wide_gen_mol_layout', 'wrnn_sparse_info', 'wrnn_set_rates', 'wrnn_get_rates', 'wrnn_debug_plan',
     'wrnn_stream_info', 'wrnn_debug_stream_bytes', 'wrnn_set_gen_wide_rows', 'wrnn_debug_wide_gen32_layout',
-    'wrnn_debug_wide_gen32_mol_layout',
+    'wrnn_debug_wide_gen32_mol_layout', 'wrnn_debug_wide_sp_pack', 'wrnn_debug_wide_sp_image', 'wrnn_sparse_wide_info',
 ]
 
 
@@ -137,6 +137,7 @@ def load_library(path=None):
         'wrnn_debug_noise': (c_int, [c_void_p, c_int, P(ctypes.c_float), c_size_t]),
         'wrnn_plan_info': (c_int, [c_void_p, P(c_int), P(c_int), P(c_int), P(c_int), c_int]),
         'wrnn_sparse_info': (c_int, [c_void_p, P(c_int), P(c_int), P(ctypes.c_double), P(c_int)]),
+        'wrnn_sparse_wide_info': (c_int, [c_void_p, P(c_int), P(c_int), P(ctypes.c_double), P(c_int)]),
         'wrnn_set_rates': (c_int, [c_void_p, ctypes.c_char_p]),
         'wrnn_get_rates': (c_int, [c_void_p, ctypes.c_char_p, c_size_t]),
         'wrnn_debug_plan': (c_int, [ctypes.c_char_p, c_int, c_int, c_int, c_int, c_int, c_int, P(c_int),
@@ -167,6 +168,11 @@ def load_library(path=None):
         'wrnn_debug_wide_gen32_layout': (c_int, [c_int]),
         'wrnn_debug_wide_gen32_mol_layout': (c_int, [c_int, c_int]),
         'wrnn_debug_logits': (c_int, [c_void_p, c_int, c_int, P(ctypes.c_float), c_size_t]),
+        'wrnn_debug_wide_sp_pack': (c_int, [P(ctypes.c_float), c_int, c_int, c_int, P(ctypes.c_float), P(c_int),
+                                            P(c_int)]),
+        'wrnn_debug_wide_sp_image': (c_int, [P(ctypes.c_float), c_int, P(ctypes.c_float), P(ctypes.c_float),
+                                             P(ctypes.c_float), c_int, P(ctypes.c_float), c_int,
+                                             P(ctypes.c_float), c_int, P(c_int), P(ctypes.c_double), P(c_int)]),
     }
     # (an A/B build given by WRNN_LIB may predate an entry point: it is left unbound)
     tolerant = host_only or bool(os.environ.get('WRNN_LIB'))

@@ -264,6 +264,18 @@ class WaveRNN:
         return dict(available=bool(av.value), last_call=bool(lc.value), density=d.value,
                     fill_f4=fill.value)
 
+    def sparse_wide_info(self):
+        """The same for wide row batches (the block-sparse wide kernel): dict(
+        available, last_call, density, fill_f4) -- whether the loaded weights have a sparse-wide
+        image, whether a launch of the last call ran it (stage `persist_wide_sp`), the live
+        fraction of the packed 1 x 4 blocks, and the fullest slot's blocks."""
+        av, lc, fill = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        d = ctypes.c_double()
+        _abi.check(self._lib.wrnn_sparse_wide_info(self._h, ctypes.byref(av), ctypes.byref(lc),
+                                                   ctypes.byref(d), ctypes.byref(fill)))
+        return dict(available=bool(av.value), last_call=bool(lc.value), density=d.value,
+                    fill_f4=fill.value)
+
     def rates(self):
         """The launch planner's rate table in effect (text, first line its source)."""
         buf = ctypes.create_string_buffer(4096)

@@ -25,6 +25,12 @@ time) and writes `key v1 .. v4` lines for the keys it found; the runtime
     MOL / Beta, one 32-row launch at k = 17 .. 32 rows per group, WRNN_PERSIST_WIDE=1 and
     WRNN_GEN_WIDE_ROWS=32; at least two fills) -> wide_gen32, wide_gen32_mol, wide_gen32_beta = base,
     per row (least squares)
+  <dir>/sp_wide_r<k>.log, <dir>/sp10_wide_r<k>.log (fatchord RAW at 9 / 10 bits on 90 %-pruned weights,
+    every launch block-sparse wide at k rows per group, WRNN_PERSIST_WIDE=1 and WRNN_SPARSE_WIDE=1), or
+    <dir>/rates.log (stage-timing lines {"bits", "rows_per_group", "kernel", "us_per_step"}; the
+    `persist_wide_sp` lines, repeats of a point averaged: profiles/wide_sp); at least two 9-bit
+    fills and one 10-bit fill -> wide_sp = base, per row (least squares over the 9-bit fills),
+    1024-class extra (mean excess of the 10-bit fills over that line)
 Later directories override earlier ones. The rotation tables keep the runtime's defaults unless
 a key is already in the file given as OUT (kept lines are carried over).
 """
@@ -109,6 +115,28 @@ def main():
                 per_row = max(per_row, 0.001)
                 keys[key] = [round(mv - per_row * mk, 3), round(per_row, 4)]
                 src[key] = d
+        pts = [(k, us_step(line_of(os.path.join(d, f'sp_wide_r{k}.log')))) for k in range(1, 17)]
+        pts = [(k, v) for k, v in pts if v is not None]
+        pts10 = [(k, us_step(line_of(os.path.join(d, f'sp10_wide_r{k}.log')))) for k in range(1, 17)]
+        pts10 = [(k, v) for k, v in pts10 if v is not None]
+        try:
+            pt = {}
+            for ln in open(os.path.join(d, 'rates.log')):
+                j = json.loads(ln) if ln.startswith('{') else {}
+                if j.get('kernel') == 'persist_wide_sp':
+                    pt.setdefault((j['bits'], j['rows_per_group']), []).append(j['us_per_step'])
+            pts += [(k, sum(v) / len(v)) for (b, k), v in sorted(pt.items()) if b == 9]
+            pts10 += [(k, sum(v) / len(v)) for (b, k), v in sorted(pt.items()) if b == 10]
+        except OSError:
+            pass
+        if len(pts) >= 2 and pts10:
+            mk, mv = sum(k for k, _ in pts) / len(pts), sum(v for _, v in pts) / len(pts)
+            per_row = sum((k - mk) * (v - mv) for k, v in pts) / sum((k - mk) ** 2 for k, _ in pts)
+            per_row = max(per_row, 0.001)
+            base = mv - per_row * mk
+            extra = max(sum(v - (base + per_row * k) for k, v in pts10) / len(pts10), 0.001)
+            keys['wide_sp'] = [round(base, 3), round(per_row, 4), round(extra, 3)]
+            src['wide_sp'] = d
     kept = []
     if os.path.exists(out):
         for ln in open(out):
