@@ -202,6 +202,17 @@ int wrnn_set_engine(wrnn_handle* h, int engine);
  * geneing, is WRNN_ERR_INVALID. Env WRNN_GEN_WIDE_ROWS=16|32 (read per call) overrides the handle's
  * setting; under WRNN_GEN_RING=0 no 32-row launch is planned. */
 int wrnn_set_gen_wide_rows(wrnn_handle* h, int rows);
+/* Time-sliced wide launches of the geneing topology (operator tuning; no reference equivalent,
+ * DESIGN.md §3.0d2 / §3.0f): on = 1 lets a call of 8 R_g rows with R_g > 16, not a multiple of 16,
+ * run as launches of 16 rows per group over rotating row sets (rows that are no multiple of 8 are
+ * padded to one) instead of a mix of wide and register-resident launches, when that is cheaper by
+ * the rate keys slice and wide_gen_slice / wide_gen_slice_mol / wide_gen_slice_beta; such a call forms its
+ * conditioning and BITS noise in-kernel. Results equal the unsliced wide launches' bit for bit.
+ * Default 0. Any other value, or 1 on a handle that is not geneing, is WRNN_ERR_INVALID. Env
+ * WRNN_GEN_SLICE=0|1 (read per call) overrides the handle's setting; WRNN_PERSIST_SLICE=0 and
+ * WRNN_GEN_RING=0 forbid the slices. With wrnn_set_gen_wide_rows(32) selected too, the cheapest
+ * of the three plans runs. */
+int wrnn_set_gen_wide_slices(wrnn_handle* h, int on);
 /* Engine that ran the last call. */
 int wrnn_last_engine(wrnn_handle* h, int* engine);
 /* Calls on this handle that fell back from PERSIST to CHAIN under WRNN_ENGINE_AUTO (the
@@ -250,7 +261,10 @@ int wrnn_get_rates(wrnn_handle* h, char* buf, size_t cap);
  * and the head's flag 4 / 32 / 64; rate keys wide_gen32, wide_gen32_mol, wide_gen32_beta; only in
  * plans whose launches are all wide), 512 the block-sparse wide image exists (fatchord RAW, with
  * flag 4; rate key wide_sp: a wide launch whose wide_sp price is strictly below its wide price is
- * planned block-sparse). bits outside 1..10, an unknown mode or more than 2^20 rows are
+ * planned block-sparse), 1024 the geneing time-sliced instances are available and selected
+ * (wrnn_set_gen_wide_slices(1); needs flag 128 of wrnn_debug_stream_bytes and the head's flag
+ * 4 / 32 / 64; priced by the rate key slice and the head's wide_gen_slice* key; the rows are padded to a
+ * multiple of 8). bits outside 1..10, an unknown mode or more than 2^20 rows are
  * WRNN_ERR_INVALID. Outputs: launches, rows per group and wide flag (1 the wide MFMA kernel, 2 a
  * block-sparse wide launch) of the first `cap`, and the row rotation's launch count (0: none). */
 int wrnn_debug_plan(const char* table, int model_type, int bits, int mode, int rows, int seq_len, int flags,
@@ -275,7 +289,8 @@ int wrnn_stream_info(wrnn_handle* h, uint64_t* p1_bytes, uint64_t* noise_bytes);
  * built-in rates (arguments and flags as there), and whether the workspace check would admit the
  * persistent engine (*persist_ok; 0: an engine='auto' call runs on CHAIN). One more flag: 128 =
  * geneing in-kernel conditioning available (the per-frame P1 form and spill-free ring instances,
- * as on a finalized geneing handle); without it a geneing call is taken to write its streams. No
+ * as on a finalized geneing handle); without it a geneing call is taken to write its streams.
+ * (With flag 1024 a sliced call writes P1 for step 0 only and no BITS noise stream.) No
  * environment switch is read: the default rule. wrnn_generate runs the same function. */
 int wrnn_debug_stream_bytes(int model_type, int bits, int mode, int rows, int seq_len, int flags,
                             double* p1_bytes, double* noise_bytes, int* persist_ok);

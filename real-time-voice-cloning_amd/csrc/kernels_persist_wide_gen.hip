@@ -5,7 +5,9 @@
 // logistics) and Beta (geneing 'RAW', WRNN_MODE_BETA, 2 logits). Calls of at most 32 rows stay on
 // k_persist_gen (the planner offers this kernel above that, or under WRNN_PERSIST_WIDE=1). The
 // 32-row ring instances (k_persist_wide_gen32, below the 16-row kernel: two column tiles per group,
-// 256 rows per launch) are opt-in (wrnn_set_gen_wide_rows).
+// 256 rows per launch) are opt-in (wrnn_set_gen_wide_rows), and so are the time-sliced ring
+// instances (k_persist_wide_gen_rot, between the two: launches of 16 rows per group over rotating
+// row sets; wrnn_set_gen_wide_slices).
 //
 // Reference step body: vocoder/models/geneing_version.py:193-205 (rnn_dims 256, fc_dims 128):
 //   x1 = I(x0) + h1'     h1' = rnn1(I(x0), h1)
@@ -133,6 +135,8 @@ struct GenLds {
     static constexpr int FAIL = NT == 1 ? 112 : 6 * kRows;   // behind the RowInfo array
     static constexpr int REG = FAIL + 4;                     // group, slot, registration result (ints)
     static constexpr int CB = REG + 12;  // b_hh1 of the slot's units [3][8], then b_f3 of its classes @32
+    // time-sliced launches: (physical row, step offset) of the group's rows, as int2
+    static constexpr int VM = CB + 64;
     // partial tiles [tile][8 v][nt][16 n][16 m], one buffer per product (fc1: nt 1, W_hh1 and fc3: 2)
     static constexpr int P = 256 * NT;
     static constexpr int F1 = P, HH = F1 + NT * WT, F3 = HH + 2 * NT * WT, TOTAL = F3 + 2 * NT * WT;
@@ -141,6 +145,7 @@ struct GenLds {
     static constexpr int P1R = TOTAL, GR = P1R + kRows * GU * 4, TOTAL_RING = GR + kRows * kGrW;
     static_assert(sizeof(RowInfo) == 24 && kRows * 6 <= FAIL, "RowInfo array overflows");
     static_assert(CB + 32 + 32 <= P && REG % 4 == 0, "slot constants overflow");
+    static_assert(VM % 2 == 0 && VM + 2 * kRowsW <= P, "virtual-row map overflows");
     static_assert(P % 4 == 0 && P1R % 4 == 0 && WT % 4 == 0, "partial tiles and P1 array: float4-aligned");
     static_assert(TOTAL_RING * sizeof(float) <= (NT == 1 ? 64 : 160) * 1024, "LDS arrays exceed the kernel's carve");
 };
@@ -310,11 +315,20 @@ __device__ __forceinline__ GenState gen_state(const PersistGenArgs& a, const Gen
     s.o_lp = c.cell && c.w < 2 && 16 * c.w + c.cul < a.n_classes ? g_logit(c.cnl, 16 * c.w + c.cul) : kNoOff;
     return s;
 }
-// MOL: the row's draws of step te into pgn
-template <int NT>
-__device__ __forceinline__ void gen_mol_draw(const PersistGenArgs& a, const GenCell<NT>& c, GenState& s, int te) {
-    const int tc = te < a.S ? te : a.S - 1;
-    if (c.cell && c.cul < kMolNoise) s.pgn = bld(mk_rsrc(a.gumbel + (size_t)tc * a.B * kMolNoise), s.o_mol, 0);
+// MOL: the row's draws of step te into pgn. ROT (time-sliced launch): te counts from the row's
+// offset `off`, so the step's base differs between the rows of a wave and the whole address is a
+// 32-bit offset into the stream (the planner and the launcher hold such a call's stream to 2 GiB)
+template <int NT, bool ROT = false>
+__device__ __forceinline__ void gen_mol_draw(const PersistGenArgs& a, const GenCell<NT>& c, GenState& s, int te,
+                                             int off = 0) {
+    if constexpr (ROT) {
+        const int tc = te < a.S - off ? te : a.S - off - 1;
+        if (c.cell && c.cul < kMolNoise)
+            s.pgn = bld(mk_rsrc(a.gumbel), (unsigned)((tc + off) * a.B * kMolNoise) * 4u + s.o_mol, 0);
+    } else {
+        const int tc = te < a.S ? te : a.S - 1;
+        if (c.cell && c.cul < kMolNoise) s.pgn = bld(mk_rsrc(a.gumbel + (size_t)tc * a.B * kMolNoise), s.o_mol, 0);
+    }
 }
 // initial x1, h1 (canonicalised: a signalling NaN in a carried state must not read as the
 // sentinel), as step t0's vectors
@@ -358,7 +372,7 @@ __device__ __forceinline__ void gen_ring_read(const GenCell<NT>& c, float (&pn)[
 // fc3 epilogue (hop 2's end), from the partials in F3
 template <int MODE, bool DBG, int NT>
 __device__ __forceinline__ void gen_pub_fc3(const PersistGenArgs& a, const GenCell<NT>& c, const GenState& s,
-                                            const float (&pn)[2], int t, unsigned seq) {
+                                            const float (&pn)[2], int t, unsigned seq, int off = 0) {
     using L = GenLds<NT>;
     const float* cb = c.lds + L::CB;
     if constexpr (MODE == 0) {
@@ -371,7 +385,7 @@ __device__ __forceinline__ void gen_pub_fc3(const PersistGenArgs& a, const GenCe
                 if (j >= c.ntc) break;
                 const int cl = a.cpw * c.w + 16 * j + c.cul;
                 const float lg = p_add(c.psum(L::F3, 2, j, c.cul), cb[32 + 16 * j + c.cul]);
-                p_dbg_logit<DBG>(a.dbg, t, c.crow, cl, a.B, a.n_classes, lg);
+                p_dbg_logit<DBG>(a.dbg, t + off, c.crow, cl, a.B, a.n_classes, lg);
                 const CandKey k = cand_key(lg, __float_as_uint(pn[j]), cl);
                 kmax_take(kh, kl, k.hi, k.lo);
             }
@@ -386,7 +400,7 @@ __device__ __forceinline__ void gen_pub_fc3(const PersistGenArgs& a, const GenCe
         float lg = 0.f;
         if (s.o_lp != kNoOff) {
             lg = p_add(c.psum(L::F3, 2, 0, c.cul), cb[32 + c.cul]);
-            p_dbg_logit<DBG>(a.dbg, t, c.crow, 16 * c.w + c.cul, a.B, a.n_classes, lg);
+            p_dbg_logit<DBG>(a.dbg, t + off, c.crow, 16 * c.w + c.cul, a.B, a.n_classes, lg);
         }
         unsigned vo = s.o_lp;
         asm volatile("" : "+v"(vo));
@@ -407,11 +421,17 @@ __device__ __forceinline__ void gen_gh1(const GenCell<NT>& c, float& g1r, float&
 }
 // ---- hop 3: the sample of step t; slot 0 stores it (BITS: with its label). Every slot forms it
 // (each needs x for its own GRU units). BITS: lane cul polls the candidates of slots 2 cul,
-// 2 cul + 1 of row cn; MOL / BETA: logits cul and 16 + cul of its row ------------------------
-template <int MODE, int NT>
+// 2 cul + 1 of row cn; MOL / BETA: logits cul and 16 + cul of its row. ROT (time-sliced launch):
+// t is the launch's step and the row's own step is t + off -- the column of its outputs, which go
+// to its physical row (the virtual-row map in LDS), and the step of its Beta draws -------------
+template <int MODE, int NT, bool ROT = false>
 __device__ __forceinline__ float gen_sample(const PersistGenArgs& a, const GenCell<NT>& c, GenState& s, int t,
-                                            unsigned seq, bool& fail) {
+                                            unsigned seq, bool& fail, int off = 0) {
     float x;
+    auto out_row = [&](int nn) {  // the call's row of the group's slot nn
+        if constexpr (ROT) return reinterpret_cast<const int2*>(c.lds + GenLds<NT>::VM)[nn].x;
+        else return c.g0 + kPG * nn;
+    };
     if constexpr (MODE == 0) {
         u4v q;
         fail |= !poll_cand_couple(c.xr, c.cell, g_cand(c.cnl, 2 * c.cul), GX_D * 4 + c.xt, key_tag(seq), a.ctl,
@@ -424,9 +444,10 @@ __device__ __forceinline__ float gen_sample(const PersistGenArgs& a, const GenCe
         if (c.w == 0 && c.cell && c.cul == 0) {
             int nn = c.cn;
             asm volatile("" : "+v"(nn));
-            const unsigned ro = (unsigned)((c.g0 + kPG * nn) * a.ld);
-            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u, (unsigned)t * 2u, 0);
-            bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)t * 4u);
+            const unsigned ro = (unsigned)(out_row(nn) * a.ld);
+            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels), ro * 2u,
+                                                  (unsigned)(t + off) * 2u, 0);
+            bst(x, mk_rsrc(a.samples), ro * 4u, (unsigned)(t + off) * 4u);
         }
     } else {
         u2v qa, qb;
@@ -444,7 +465,8 @@ __device__ __forceinline__ float gen_sample(const PersistGenArgs& a, const GenCe
             double gv = 0.0;
             if (c.cell && c.cul < 2) {
                 const RowInfo& ri = c.row(c.cn);
-                gv = gamma_mt((double)expf(la), (uint32_t)c.cul, (uint32_t)t, (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
+                gv = gamma_mt((double)expf(la), (uint32_t)c.cul, (uint32_t)(t + off), (uint32_t)ri.fold, ri.stream, a.k0,
+                              a.k1);
             }
             const double gy = __shfl(gv, base + 1);
             float xv = 0.f;
@@ -461,16 +483,17 @@ __device__ __forceinline__ float gen_sample(const PersistGenArgs& a, const GenCe
         if (c.w == 0 && c.cell && c.cul == 0) {
             int nn = c.cn;
             asm volatile("" : "+v"(nn));
-            bst(x, mk_rsrc(a.samples), (unsigned)((c.g0 + kPG * nn) * a.ld) * 4u, (unsigned)t * 4u);
+            bst(x, mk_rsrc(a.samples), (unsigned)(out_row(nn) * a.ld) * 4u, (unsigned)(t + off) * 4u);
         }
     }
     return x;
 }
 // ---- GRU1 of step t + 1 for the slot's units -> x1, h1 ---------------------------------------
 //   gi = W_ih1 (cI + w0 x) + b_ih1 = P1 + v x ; x1 = (cI + w0 x) + h1
+//   (returns the cell's x1: with h1 the chunk state a time-sliced launch saves at its end)
 template <int NT>
-__device__ __forceinline__ void gen_gru1_pub(const GenCell<NT>& c, GenState& s, float x, const float4& pp, float g1r,
-                                             float g1z, float g1n, unsigned seq) {
+__device__ __forceinline__ float gen_gru1_pub(const GenCell<NT>& c, GenState& s, float x, const float4& pp, float g1r,
+                                              float g1z, float g1n, unsigned seq) {
     float x1 = 0.f;
     if (c.gcell) {
         s.h1r = p_gru(fmaf(s.vr, x, pp.x), fmaf(s.vz, x, pp.y), fmaf(s.vn, x, pp.z), g1r, g1z, g1n, s.h1r);
@@ -478,6 +501,7 @@ __device__ __forceinline__ void gen_gru1_pub(const GenCell<NT>& c, GenState& s, 
     }
     c.pub(GX_X1, GS_X, c.o_px, x1, seq + 1u);
     c.pub(GX_H1, GS_X, c.o_px, s.h1r, seq + 1u);
+    return x1;
 }
 // the step's end: progress for the host's callback, and its abort (seen at the next step's check)
 template <int NT>
@@ -546,13 +570,14 @@ __device__ __forceinline__ bool g_poll2(rsrc_t xr, unsigned voff, unsigned so, b
 // P1(tau) of (row ri, unit 8 w + j) from the per-frame tables, k_p1_expand's fma chain without its
 // zero tap (as kernels_persist_wide.hip p1_make): positions >= L take the zero frame at fbase
 // (bias only), frames outside the utterance its zeroed guard slots; tau is clamped at the row's
-// last step, as the stream read clamps it.
+// last step, as the stream read clamps it. In a time-sliced launch tau counts from the row's
+// offset `off` (ri.rel0 carries it already), so the row's last step is S - 1 - off.
 struct RingP1Taps {
     float4 tk, tq[4], ta;
 };
 __device__ __forceinline__ void ring_p1_load(const PersistGenRingArgs& a, const RowInfo& ri, int w, int j, int tau,
-                                             RingP1Taps& o) {
-    const int tc = tau < a.S ? tau : a.S - 1;
+                                             RingP1Taps& o, int off = 0) {
+    const int tc = tau < a.S - off ? tau : a.S - off - 1;
     int uu = GU * w + j;
     asm volatile("" : "+v"(uu));
     const unsigned p = (unsigned)(ri.rel0 + tc);
@@ -587,12 +612,13 @@ __device__ __forceinline__ float4 ring_p1_finish(const RingP1Taps& o) {
 // class quad, absolute step, fold, stream). Thread j of a row takes class j of slot w (cpw 16,
 // ntc 1) or the pair 2 j, 2 j + 1 (cpw 32, ntc 2: one Philox block for both): the Philox words of
 // the thread's class (wd) and, ntc 2, of class c + 1 of the same quad (wd1; c is even)
-// (a padding row repeats the last real row: drawn and never used)
+// (a padding row repeats the last real row: drawn and never used); the absolute step of a
+// time-sliced launch's row is tau + off
 __device__ __forceinline__ void ring_noise_words(const PersistGenRingArgs& a, const RowInfo& ri, int w, int ntc, int j,
-                                                 int tau, uint32_t& wd, uint32_t& wd1) {
+                                                 int tau, uint32_t& wd, uint32_t& wd1, int off = 0) {
     int c = a.cpw * w + (ntc == 2 ? 2 * j : j);
     asm volatile("" : "+v"(c));
-    const U4 o = philox4x32_10((uint32_t)(c >> 2), (uint32_t)tau, (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
+    const U4 o = philox4x32_10((uint32_t)(c >> 2), (uint32_t)(tau + off), (uint32_t)ri.fold, ri.stream, a.k0, a.k1);
     const int q = c & 3;
     wd = q == 0 ? o.x : q == 1 ? o.y : q == 2 ? o.z : o.w;
     wd1 = q == 0 ? o.y : o.w;
@@ -604,9 +630,9 @@ __device__ __forceinline__ float* ring_noise_dst(float* lds, int ntc, int n, int
 }
 template <class L>
 __device__ __forceinline__ void ring_noise_make(const PersistGenRingArgs& a, float* lds, int w, int ntc, int n, int j,
-                                                int tau) {
+                                                int tau, int off = 0) {
     uint32_t wd, wd1;
-    ring_noise_words(a, reinterpret_cast<const RowInfo*>(lds + L::RI)[n], w, ntc, j, tau, wd, wd1);
+    ring_noise_words(a, reinterpret_cast<const RowInfo*>(lds + L::RI)[n], w, ntc, j, tau, wd, wd1, off);
     float* dst = ring_noise_dst<L>(lds, ntc, n, j);
     dst[0] = __uint_as_float(gumbel_q_of(wd));
     if (ntc == 2) {
@@ -615,9 +641,10 @@ __device__ __forceinline__ void ring_noise_make(const PersistGenRingArgs& a, flo
     }
 }
 template <class L>
-__device__ __forceinline__ void ring_p1_make(const PersistGenRingArgs& a, float* lds, int w, int n, int j, int tau) {
+__device__ __forceinline__ void ring_p1_make(const PersistGenRingArgs& a, float* lds, int w, int n, int j, int tau,
+                                             int off = 0) {
     RingP1Taps taps;
-    ring_p1_load(a, reinterpret_cast<const RowInfo*>(lds + L::RI)[n], w, j, tau, taps);
+    ring_p1_load(a, reinterpret_cast<const RowInfo*>(lds + L::RI)[n], w, j, tau, taps, off);
     reinterpret_cast<float4*>(lds + L::P1R)[n * GU + j] = ring_p1_finish(taps);
 }
 }  // namespace
@@ -758,6 +785,132 @@ __global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen(
         gen_step_end(a, c, t);
     }
     if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
+}
+
+// ---- time-sliced ring instances ----------------------------------------------
+// The 16-row ring instance over a virtual-row map (PersistGenArgs::vmap): slot r of group g is the
+// virtual row g + 8 r, which a.vmap maps to (physical row, step offset off). The launch runs its
+// own steps t = 0 .. t1 - 1 with launch-local exchange tags (seq = t + 1); the row's step is
+// t + off. a.rows is the launch's RowInfo table by virtual row with rel0 advanced by off, so the
+// frame lookups (fc1 conditioning, P1) take t as it is; off enters the step clamp of P1, the Philox
+// step of the noise and of the Beta draws, the MOL draw row, the column of the outputs and the
+// captured logit's step. The row's x1, h1 come from its chunk state (k_persist_gen_init, or the
+// launch that ran the row before) and go back there at the launch's end. A kernel of its own, so
+// that the instances above keep their code; the step is theirs piece by piece (gen_*, ring_*), so a
+// row's outputs are the unsliced launch's bit for bit.
+template <int MODE, bool DBG>
+__global__ __launch_bounds__(kPT, 1) void k_persist_wide_gen_rot(PersistGenRingArgs a) {
+    static_assert(MODE >= 0 && MODE <= 2, "BITS, MOL or BETA");
+    using L = GenLds<1>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int g, w;
+    if (!gen_register<L>(a.ctl, lds, g, w)) return;
+    const int tid = threadIdx.x;
+    GenCell<1> c = gen_cell<MODE, 1>(a, lds, g, w);
+    // the cell's step offset; its row (c.crow: chunk state, draw stream, captured logits) becomes
+    // the physical one (gen_cell left the virtual row there: below 8 R, inside the map)
+    const int2 cvm = a.vmap[c.crow];
+    c.crow = cvm.x;
+    const int coff = cvm.y;
+    const int v = c.v;
+    const bool bvalid = c.bn < c.R;
+    const unsigned o_cx = g_cons_x(v, c.l), o_cy = g_cons_y(v, c.l);
+    float4 wq[kWgq];
+    gen_load_weights(a, c, wq);
+    gen_setup_lds(a, c);
+    if (tid < c.R) reinterpret_cast<int2*>(lds + L::VM)[tid] = a.vmap[c.g0 + kPG * tid];
+    GenState s = gen_state(a, c);
+    const rsrc_t fcr = mk_rsrc(a.fcond);
+    // waves 4-7 form the rows' P1 and noise cells as in the plain ring instance, each row at its
+    // own offset
+    auto ring_make = [&](int t_noise, int t_p1) {
+        const int i = tid - 256;
+        const int2* vm = reinterpret_cast<const int2*>(lds + L::VM);
+        if (i < GU * c.R) ring_p1_make<L>(a, lds, w, i >> 3, i & 7, t_p1, vm[i >> 3].y);
+        if constexpr (MODE == 0)
+            if (i < 16 * c.R) ring_noise_make<L>(a, lds, w, c.ntc, i >> 4, i & 15, t_noise, vm[i >> 4].y);
+    };
+    __syncthreads();
+    // prologue: the noise of the row's first step and P1 of its second
+    if (v >= 4) ring_make(0, 1);
+    if constexpr (MODE == 1) {
+        gen_mol_draw<1, true>(a, c, s, 0, coff);
+        s.pg = s.pgn;
+    }
+    if (v < 4) gen_pub_initial(a, c, s);
+    bool fail = false;
+    u4v cc[2];
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[0] = p_now();
+    for (int t = 0; t < a.t1; ++t) {
+        const unsigned seq = (unsigned)t + 1u;
+        const float pc = gen_fc1_cond(a, c, fcr, t);
+        [[maybe_unused]] float pn[2] = {0.f, 0.f};
+        float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (MODE == 1) gen_mol_draw<1, true>(a, c, s, t + 1, coff);
+        // ---- hop 1: x1 of every slot -> fc1 -> y1 -------------------------------------------
+        fail |= !g_poll<2>(c.xr, o_cx, g_slot(GX_X1, GS_X, seq), bvalid, cc, a.ctl, c.wh(1), (unsigned)t);
+        {
+            v4f acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) acc = mfma4(f4c(wq[4 + ks / 4], ks % 4), u4c(cc[ks >> 2], ks & 3), acc);
+            c.put(L::F1, 1, 0, 0, acc);
+        }
+        if (fail) lds[L::FAIL] = 1.f;
+        lds_barrier();
+        if (lds[L::FAIL] != 0.f) return;
+        if (v < 4) {
+            gen_pub_y1(c, pc, seq);
+            gen_ring_read<MODE>(c, pn, pp);
+        }
+        // ---- in the wait for y1: h1 of every slot -> W_hh1 h1 --------------------------------
+        fail |= !g_poll<2>(c.xr, o_cx, g_slot(GX_H1, GS_X, seq), bvalid, cc, a.ctl, c.wh(2), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const float b = u4c(cc[ks >> 2], ks & 3);
+                a0 = mfma4(f4c(wq[ks / 4], ks % 4), b, a0);
+                a1 = mfma4(f4c(wq[2 + ks / 4], ks % 4), b, a1);
+            }
+            c.put(L::HH, 2, 0, 0, a0);
+            c.put(L::HH, 2, 0, 1, a1);
+        }
+        // ---- hop 2: y1 of every slot -> fc3 -> the slot's candidate (logits) of every row ------
+        fail |= !g_poll<1>(c.xr, o_cy, g_slot(GX_Y1, GS_Y, seq), bvalid, cc, a.ctl, c.wh(3), (unsigned)t);
+        {
+            v4f a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const float b = u4c(cc[0], ks);
+                a0 = mfma4(f4c(wq[6], ks), b, a0);
+                if (c.ntc == 2) a1 = mfma4(f4c(wq[7], ks), b, a1);
+            }
+            c.put(L::F3, 2, 0, 0, a0);
+            if (c.ntc == 2) c.put(L::F3, 2, 0, 1, a1);
+        }
+        if (fail) lds[L::FAIL] = 1.f;
+        lds_barrier();
+        if (v < 4) {
+            float g1r, g1z, g1n;
+            gen_pub_fc3<MODE, DBG>(a, c, s, pn, t, seq, coff);
+            gen_gh1(c, g1r, g1z, g1n);
+            const float x = gen_sample<MODE, 1, true>(a, c, s, t, seq, fail, coff);
+            if (fail) lds[L::FAIL] = 1.f;  // seen by every wave at the next step's check
+            s.x1c = gen_gru1_pub(c, s, x, pp, g1r, g1z, g1n, seq);
+        } else {
+            ring_make(t + 1, t + 2);  // (the row's last step: P1 clamped, its GRU1 goes unused)
+        }
+        gen_step_end(a, c, t);
+    }
+    if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
+    // x1, h1 of the launch's last GRU1 (the row's step off + t1) back into the chunk state, for the
+    // launch that runs the row next. A cell reads and writes its own two words only, and the next
+    // launch starts after this one has finished
+    if (c.gcell && !fail && lds[L::FAIL] == 0.f) {
+        float* st = a.st + (size_t)c.crow * 2 * GH;
+        st[c.cu] = s.x1c;
+        st[GH + c.cu] = s.h1r;
+    }
 }
 
 // ---- 32-row ring instances ------------------------------------------------------------------
@@ -943,7 +1096,7 @@ hipError_t gen_reset_xbuf(float* xbuf, size_t floats, hipStream_t s) {
     return hipGetLastError();
 }
 
-// The three kernel families, instance <MODE, DBG> of each, and the one (mode x DBG) dispatch:
+// The four kernel families, instance <MODE, DBG> of each, and the one (mode x DBG) dispatch:
 // f(instance) for the family's instance of (mode 0 .. 2, dbg), the kernel as decltype(k)::value
 struct Gen16Stream {
     using Args = PersistGenArgs;
@@ -959,6 +1112,11 @@ struct Gen32Ring {
     using Args = PersistGenRingArgs;
     template <int MODE, bool DBG>
     static constexpr auto k = k_persist_wide_gen32<MODE, DBG>;
+};
+struct Gen16Rot {
+    using Args = PersistGenRingArgs;
+    template <int MODE, bool DBG>
+    static constexpr auto k = k_persist_wide_gen_rot<MODE, DBG>;
 };
 template <class Fam, int MODE, bool DBG>
 using GenInst = std::integral_constant<void (*)(typename Fam::Args), Fam::template k<MODE, DBG>>;
@@ -993,10 +1151,15 @@ int gen_scratch_max(int mode) {
 }
 // whole launches (t0 = 0: x1, h1 of k_persist_gen_init) of BITS rows with 512 or 1024 classes
 // (1 or 2 fc3 tiles of 16 per slot), of MOL rows (30 logits; the draws come from the k_mol_noise
-// stream) or of BETA rows (2): one tile in slots 0 and 1; no rotated or time-sliced instance
-bool gen_args_ok(const PersistGenArgs& a, int max_rows) {
-    if (a.rb < 0 || a.nr < 1 || a.nr > max_rows || a.rb + kPG * a.nr > a.B || a.t0 != 0 || a.t1 != a.S ||
-        a.vmap != nullptr || a.wwide == nullptr)
+// stream) or of BETA rows (2): one tile in slots 0 and 1. rot: a time-sliced launch instead (its
+// virtual-row map, t1 <= S steps from every row's chunk state)
+bool gen_args_ok(const PersistGenArgs& a, int max_rows, bool rot = false) {
+    if (a.rb < 0 || a.nr < 1 || a.nr > max_rows || a.rb + kPG * a.nr > a.B || a.t0 != 0 || a.wwide == nullptr)
+        return false;
+    // (a time-sliced launch indexes its map and its RowInfo table by virtual row g + 8 r: both hold
+    // 8 nr entries, so the launch starts at row 0)
+    if (rot ? a.vmap == nullptr || a.rb != 0 || a.t1 < 1 || a.t1 > a.S || a.st == nullptr
+            : a.vmap != nullptr || a.t1 != a.S)
         return false;
     if (a.mode == 1) return a.cpw == 16 && a.n_classes == 30 && a.gumbel != nullptr;
     if (a.mode == 2) return a.cpw == 16 && a.n_classes == 2;
@@ -1008,7 +1171,7 @@ bool gen_ring_args_ok(const PersistGenRingArgs& a) {
 }
 template <class Fam>
 hipError_t gen_launch(const typename Fam::Args& a, int max_rows, size_t lds, hipStream_t s) {
-    if (!gen_args_ok(a, max_rows)) return hipErrorInvalidValue;
+    if (!gen_args_ok(a, max_rows, std::is_same_v<Fam, Gen16Rot>)) return hipErrorInvalidValue;
     return gen_dispatch<Fam>(a.mode, a.dbg.out != nullptr,
                              [&](auto k) { return persist_launch<decltype(k)::value>(lds, a, s); });
 }
@@ -1034,6 +1197,22 @@ hipError_t launch_persist_wide_gen(const PersistGenArgs& a, hipStream_t s) {
 hipError_t launch_persist_wide_gen_ring(const PersistGenRingArgs& a, hipStream_t s) {
     if (!gen_ring_args_ok(a) || persist_wide_gen_ring_scratch(a.mode) != 0) return hipErrorInvalidValue;
     return gen_launch<Gen16Ring>(a, kPWideRows, persist_wide_gen_lds_bytes(), s);
+}
+
+// ---- time-sliced ring instances: launch side -----------------------------------------------
+// scratch bytes of the mode's time-sliced instances (the larger of production and DBG); -1: none
+int persist_wide_gen_rot_scratch(int mode) { return gen_scratch_max<Gen16Rot>(mode); }
+// the rule of the 16-row ring instances: no scratch; Beta at most its 16-byte frame
+bool persist_wide_gen_rot_usable(int mode) {
+    const int sc = persist_wide_gen_rot_scratch(mode);
+    return sc >= 0 && sc <= (mode == 2 ? 16 : 0);
+}
+// a launch of t1 <= S steps over the rows of a.vmap (a.rows: the launch's table by virtual row).
+// The MOL instance addresses the whole draw stream [S][B][kMolNoise] with a 32-bit offset
+hipError_t launch_persist_wide_gen_rot(const PersistGenRingArgs& a, hipStream_t s) {
+    if (!gen_ring_args_ok(a) || !persist_wide_gen_rot_usable(a.mode)) return hipErrorInvalidValue;
+    if (a.mode == 1 && !((double)a.S * a.B * kMolNoise * 4.0 < 2147483648.0)) return hipErrorInvalidValue;
+    return gen_launch<Gen16Rot>(a, kPWideRows, persist_wide_gen_lds_bytes(), s);
 }
 
 // ---- 32-row ring instances: launch side ---------------------------------------------------

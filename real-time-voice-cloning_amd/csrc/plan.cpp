@@ -48,6 +48,9 @@ const RateKey kRateKeys[] = {
     {"wide_gen32", RATE_AT(R.wide_gen32), 2},
     {"wide_gen32_mol", RATE_AT(R.wide_gen32_mol), 2},
     {"wide_gen32_beta", RATE_AT(R.wide_gen32_beta), 2},
+    {"wide_gen_slice", RATE_AT(R.wide_gen_slice), 2},
+    {"wide_gen_slice_mol", RATE_AT(R.wide_gen_slice_mol), 2},
+    {"wide_gen_slice_beta", RATE_AT(R.wide_gen_slice_beta), 2},
     {"slice", RATE_AT(R.slice), 2},
     {"rot9", RATE_AT(R.rot9 + 1), kPNR},
     {"rot9_sp", RATE_AT(R.rot9_sp + 1), kPNR},
@@ -71,7 +74,9 @@ struct WideHead {
     bool mol_bound;   // its launches index the k_mol_noise stream in 32 bits (wide_fits below)
     int max_scratch;  // scratch bytes accepted (Beta: the frame k_persist_gen BETA is accepted with)
     RateAt key32;     // geneing: the 32-row ring instances' key (17 .. 32 rows per group)
-    bool slices;      // time-sliced launches exist (P1 formed in-kernel: fatchord ring, runtimeracer)
+    bool slices;      // time-sliced launches are planned by default (P1 formed in-kernel: fatchord ring,
+                      // runtimeracer); geneing has them opt-in (PlanIn::gen_slices) ...
+    RateAt key_slice; // ... on instances of their own, priced by their own key
 };
 const WideHead kWideHeads[3][3] = {  // [fatchord | runtimeracer | geneing][RAW | MOL | Beta]
     {{RATE_AT(R.wide), true, false, false, 0, nullptr, true},
@@ -80,9 +85,10 @@ const WideHead kWideHeads[3][3] = {  // [fatchord | runtimeracer | geneing][RAW 
      {RATE_AT(R.wide_rr_mol), false, true, true, 0, nullptr, true}},
     // (the geneing kernel forms the MOL stream's address of every step in 64 bits: its 16-row
     // launches have no 2-GiB bound; plan_call holds only the 32-row plan to one)
-    {{RATE_AT(R.wide_gen), false, true, false, 0, RATE_AT(R.wide_gen32), false},
-     {RATE_AT(R.wide_gen_mol), false, true, false, 0, RATE_AT(R.wide_gen32_mol), false},
-     {RATE_AT(R.wide_gen_beta), false, true, false, 16, RATE_AT(R.wide_gen32_beta), false}},
+    {{RATE_AT(R.wide_gen), false, true, false, 0, RATE_AT(R.wide_gen32), false, RATE_AT(R.wide_gen_slice)},
+     {RATE_AT(R.wide_gen_mol), false, true, false, 0, RATE_AT(R.wide_gen32_mol), false, RATE_AT(R.wide_gen_slice_mol)},
+     {RATE_AT(R.wide_gen_beta), false, true, false, 16, RATE_AT(R.wide_gen32_beta), false,
+      RATE_AT(R.wide_gen_slice_beta)}},
 };
 
 int gcd_i(int a, int b) { return b ? gcd_i(b, a % b) : a; }
@@ -395,13 +401,23 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
         }
     }
     // time-sliced wide launches, when cheaper than the plan above by the same rates (P1 formed
-    // in-kernel: the fatchord ring, runtimeracer per frame)
-    if (head_ok && hd->slices && (in.fat ? in.p1ring : in.rr_frames) && !out.lplan.empty() && !in.slice_off &&
-        in.wmode && in.wide_rot_scr == 0) {
+    // in-kernel: the fatchord ring, runtimeracer per frame). geneing: opt-in (gen_slices: the ring
+    // can be taken and the sliced instance is within its scratch rule), where the head's wide
+    // launches are offered; planned over the rows padded to the 8 groups (padding rows repeat the
+    // last real row, as in the plain launches), the MOL draw stream held to the 2 GiB its sliced
+    // instance indexes in 32 bits
+    const int Bs = in.gen ? kPG * ((B + kPG - 1) / kPG) : B;
+    const bool fr_slices = hd && hd->slices && (in.fat ? in.p1ring : in.rr_frames) && in.wide_rot_scr == 0;
+    const bool gen_slices = hd && in.gen && in.gen_slices && in.nr_max <= 0 &&
+                            ((in.wide_scr >= 0 && in.wide_scr <= hd->max_scratch) || in.allow_wide_scratch) &&
+                            (!mol || (double)S * Bs * kMolNoise * 4.0 < 2147483648.0);
+    if (head_ok && (fr_slices || gen_slices) && !out.lplan.empty() && !in.slice_off && in.wmode) {
         std::vector<WLaunch> sl;
-        if (plan_wide_slices(B, S, sl)) {
+        if (plan_wide_slices(Bs, S, sl)) {
             double cost = R.slice[0] * (sl.size() - 1);  // (an extra launch: weights, ring prologue)
-            for (const auto& L : sl) cost += L.steps * wide_cost(L.nr);
+            // (the geneing slices run on instances of their own: the head's wide_gen_slice* key)
+            const double* ks = gen_slices ? hd->key_slice(R) : nullptr;
+            for (const auto& L : sl) cost += L.steps * (ks ? ks[0] + ks[1] * L.nr : wide_cost(L.nr));
             if (cost < R.slice[1] * out.plan_us * S) {
                 out.lplan.clear();
                 for (int j = 0; j < (int)sl.size(); ++j) out.lplan.push_back({0, sl[j].nr, true, j});
@@ -411,7 +427,8 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
     }
     for (auto& L : out.lplan) L.sp = L.wide && wide_is_sp(L.nr);
     const auto& lp = out.lplan;
-    out.Bplan = lp.empty() ? B : !out.wrot.empty() ? B : lp.back().rb + kPG * lp.back().nr;
+    // (time-sliced: the rows the slices were planned for -- B itself for fatchord and runtimeracer)
+    out.Bplan = lp.empty() ? B : !out.wrot.empty() ? Bs : lp.back().rb + kPG * lp.back().nr;
     // P1 ring (fatchord): on unless a register-resident launch spills more with it than with the
     // stream (MOL at 3 rows per group: one register, 6.87 against 6.53 us per step); the sparse
     // instances exist with the ring only
@@ -462,8 +479,8 @@ void plan_call(const PlanIn& in, const PlanRates& R, PlanOut& out) {
 //   noise: the extent of the [S][Bp][n] Gumbel (RAW) or [S][Bp][kMolNoise] MOL stream; 0 when every
 //          launch draws in-kernel (Beta; RAW calls of in-kernel-noise wide launches only)
 // geneing ring (gen_frames: the per-frame P1 form exists and the ring instances run spill-free):
-// only calls whose launches are all wide, never time-sliced. sw = WRNN_GEN_RING: 1 the ring where
-// possible, 0 the streams, -1 the default -- the ring when the streams would not fit the
+// only calls whose launches are all wide (time-sliced ones are ring instances). sw =
+// WRNN_GEN_RING: 1 the ring where possible, 0 the streams, -1 the default -- the ring when the streams would not fit the
 // workspace cap, or when the head's measured call time is not above the stream form's
 // (kGenRingDefault).
 // The cap: fatchord and runtimeracer keep the whole-call bound S Bp (4 H + n) 4 bytes whatever
@@ -489,13 +506,13 @@ StreamPlan plan_streams(const PlanIn& in, const PlanOut& out, bool p1x4, bool ge
     if (in.gen) {
         const double cap_p1 = rows_steps * 4 * H * 4.0;  // (P1 and cI: 4 H floats either way)
         const bool streams_fit = cap_p1 + noise <= kPersistWsBytes;
-        const bool can = gen_frames && all_wide && out.wrot.empty() && in.mode >= 0 && in.mode <= 2;
+        const bool can = gen_frames && all_wide && in.mode >= 0 && in.mode <= 2;
         sp.gen_ring = can && sw != 0 && (sw == 1 || !streams_fit || kGenRingDefault[in.mode]);
-        // (a 32-row launch exists only as a ring instance: plan_call offers it only where `can`
-        // holds and the switch is not 0, so its plan always takes the ring)
+        // (a 32-row launch and a time-sliced one exist only as ring instances: plan_call offers them
+        // only where `can` holds and the switch is not 0, so their plans always take the ring)
         bool any32 = false;
         for (const auto& L : out.lplan) any32 |= L.wide && L.nr > kPWideRows;
-        if (any32) sp.gen_ring = can && sw != 0;
+        if (any32 || !out.wrot.empty()) sp.gen_ring = can && sw != 0;
         if (sp.gen_ring) {
             sp.p1_stream = false;
             if (raw) noise = 0.0;  // (MOL keeps its k_mol_noise stream)
@@ -534,7 +551,8 @@ int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_len, int
     // every variant spill-free. (128, geneing in-kernel conditioning, enters the plan only through
     // 256: the geneing 32-row ring instances are available and selected -- it needs 128 and the
     // head's flag 4 / 32 / 64; wrnn_debug_stream_bytes); 512 the block-sparse wide image (fatchord
-    // RAW, with flag 4)
+    // RAW, with flag 4); 1024: the geneing time-sliced instances are available and selected (needs
+    // 128 and the head's flag, like 256)
     in.sp = in.fat && (flags & 1) && (flags & 2) && (mode == WRNN_MODE_RAW || mode == WRNN_MODE_MOL);
     in.force_sp = in.sp && (flags & 8);
     in.p1ring = in.fat && (flags & 2);
@@ -546,6 +564,7 @@ int debug_plan_in(int model_type, int bits, int mode, int rows, int seq_len, int
     in.has_wide = (flags & head_flag) != 0;
     in.has_wide_sp = (flags & 512) && in.fat && raw && in.has_wide;
     in.gen32 = (flags & 256) && (flags & 128) && in.gen && in.has_wide;
+    in.gen_slices = (flags & 1024) && (flags & 128) && in.gen && in.has_wide;
     for (int c = 1; c <= kPNR; ++c) in.ok_reg[c] = true;
     return WRNN_OK;
 }

@@ -59,6 +59,14 @@ struct PlanRates {
     double wide_gen32[2] = {6.347, 0.0066};
     double wide_gen32_mol[2] = {3.992, 0.0222};
     double wide_gen32_beta[2] = {6.001, 0.0835};
+    // the time-sliced instances of that kernel (k_persist_wide_gen_rot, wrnn_set_gen_wide_slices),
+    // base + row x r: BITS 3.591, MOL 2.947, Beta 5.256 us per step at 16 rows per group, the medians
+    // of nine sliced calls each (profiles/wide_gen_slices/gen_slice{,_mol,_beta}_r16.log); a sliced
+    // launch runs 16 rows per group but for the short tails, so the per-row terms are the unsliced
+    // keys' (tools/make_rates.py)
+    double wide_gen_slice[2] = {3.46, 0.0082};
+    double wide_gen_slice_mol[2] = {2.797, 0.0094};
+    double wide_gen_slice_beta[2] = {4.728, 0.033};
     double slice[2] = {60.0, 0.98};                        // us per extra launch, gain threshold
     // rotation: rates of the rotated instance's two bodies by rows per group (the (q + 1)-row
     // one at its single-launch rate; the q-row one the best split measured, §3.0e)
@@ -130,6 +138,9 @@ struct PlanIn {
     // WRNN_GEN_WIDE_ROWS) and can run -- spill-free, and the call can take the ring (the per-frame
     // P1 form exists, WRNN_GEN_RING is not 0): established before a 32-row launch is priced
     bool gen32 = false;
+    // geneing: the head's time-sliced ring instances are selected (wrnn_set_gen_wide_slices / env
+    // WRNN_GEN_SLICE) and can run, under the same conditions
+    bool gen_slices = false;
     int scr[2][kPNR + 1] = {};     // fatchord k_persist [stream | ring][nr]
     int scr_sp[kPNR + 1] = {};     // sparse instances
     int scr_rot[2][kPNR + 1] = {}; // rotated instance of this topology / mode [dense | sparse][nr]

@@ -2,6 +2,7 @@
 // walks the plan grid of tools/plan_dump.py natively and asserts the invariants of every plan, feeds
 // parse_rates well- and ill-formed tables, and calls the handle-free wrnn_debug_* entry points with
 // bad arguments. Exit status 0: every check held (the sanitizers abort the run otherwise).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +45,7 @@ const int kSeq[] = {63, 64, 1200, 6000, 12100, 14000};
 std::vector<int> flag_sets(int model) {
     const std::vector<int> bits = model == WRNN_MODEL_FATCHORD       ? std::vector<int>{1, 2, 4, 8}
                                   : model == WRNN_MODEL_RUNTIMERACER ? std::vector<int>{2, 4, 16}
-                                                                     : std::vector<int>{4, 32, 64, 128, 256};
+                                                                     : std::vector<int>{4, 32, 64, 128, 256, 1024};
     std::vector<int> sets;
     for (int s = 0; s < (1 << bits.size()); ++s) {
         int f = 0;
@@ -59,9 +60,11 @@ std::vector<int> flag_sets(int model) {
 // every physical row of a rotated / time-sliced plan runs exactly S steps, each launch from the
 // step its earlier launches left it at
 void check_maps(const Head& h, const PlanIn& in, const PlanOut& out) {
-    std::vector<long> done(in.B, 0);
+    // (geneing slices are planned for the rows padded to the 8 groups: the padding rows run too)
+    const int nrows = std::max(in.B, out.wrot.empty() ? 0 : out.Bplan);
+    std::vector<long> done(nrows, 0);
     auto take = [&](const VRow& v, int steps) {
-        REQUIRE(v.row >= 0 && v.row < in.B, "%s rows %d: mapped row %d", h.name, in.B, v.row);
+        REQUIRE(v.row >= 0 && v.row < nrows, "%s rows %d: mapped row %d", h.name, in.B, v.row);
         REQUIRE(v.off == done[v.row], "%s rows %d: row %d starts at %d after %ld steps", h.name, in.B, v.row, v.off,
                 done[v.row]);
         done[v.row] += steps;
@@ -87,7 +90,7 @@ void check_maps(const Head& h, const PlanIn& in, const PlanOut& out) {
                 for (int r = 0; r < nr; ++r) take(P.vmap[j * nv + g + (size_t)kPG * r], it);
             }
     }
-    for (int r = 0; r < in.B; ++r) REQUIRE(done[r] == in.S, "%s rows %d: row %d ran %ld steps", h.name, in.B, r, done[r]);
+    for (int r = 0; r < nrows; ++r) REQUIRE(done[r] == in.S, "%s rows %d: row %d ran %ld steps", h.name, in.B, r, done[r]);
 }
 
 void check_plan(const Head& h, int rows, int S, int flags) {
@@ -117,6 +120,9 @@ void check_plan(const Head& h, int rows, int S, int flags) {
                 h.name, rows, L.nr);
     if (!mapped) REQUIRE(out.Bplan == rb, "%s rows %d: Bplan %d, launches end at %d", h.name, rows, out.Bplan, rb);
     REQUIRE(out.Bplan >= rows, "%s rows %d: Bplan %d", h.name, rows, out.Bplan);
+    if (!out.wrot.empty())  // sliced: the rows themselves; geneing pads them to the 8 groups
+        REQUIRE(out.Bplan == (in.gen ? kPG * ((rows + kPG - 1) / kPG) : rows), "%s rows %d: sliced for %d rows", h.name, rows,
+                out.Bplan);
     REQUIRE(mapped == (!out.wrot.empty() || out.rot.K > 0) && !(out.rot.K > 0 && !out.wrot.empty()),
             "%s rows %d: maps without mapped launches", h.name, rows);
     if (mapped) check_maps(h, in, out);
@@ -133,7 +139,11 @@ void check_plan(const Head& h, int rows, int S, int flags) {
             REQUIRE(sp.persist_ok == (rows_steps * (4 * (in.fat ? kPH : kRH) + in.n) * 4.0 <= kPersistWsBytes) &&
                         (!sp.persist_ok || sp.p1_bytes + sp.noise_bytes <= kPersistWsBytes),
                     "%s rows %d S %d: persist_ok %d", h.name, rows, S, sp.persist_ok);
-        REQUIRE(!sp.gen_ring || (in.gen && all_wide && !mapped && sw != 0 && !sp.p1_stream), "%s rows %d: ring", h.name, rows);
+        // (the ring: all-wide geneing plans, plain or time-sliced, never a rotation; a sliced plan
+        // always takes it unless the switch forbids it)
+        REQUIRE(!sp.gen_ring || (in.gen && all_wide && out.rot.K == 0 && sw != 0 && !sp.p1_stream), "%s rows %d: ring",
+                h.name, rows);
+        REQUIRE(!(in.gen && !out.wrot.empty() && sw != 0) || sp.gen_ring, "%s rows %d: slices without the ring", h.name, rows);
     }
 }
 

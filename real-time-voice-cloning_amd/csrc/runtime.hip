@@ -184,6 +184,7 @@ struct wrnn_handle {
     bool p1_stream = false;    // this call writes the [S][B][4H] P1 stream (other kernels)
     bool gen_ring = false;     // geneing: every launch is wide and forms P1 / the noise in-kernel
     int gen_wide_rows = kPWideRows;  // wrnn_set_gen_wide_rows: 16, or 32 (the 32-row ring instances)
+    bool gen_wide_slices = false;    // wrnn_set_gen_wide_slices: geneing time-sliced wide launches
     double last_p1_bytes = 0, last_noise_bytes = 0;  // the per-step streams of the last call (wrnn_stream_info)
     bool sparse_call = false;  // this call's k_persist launches run the sparse instances
     bool sparse_wide_call = false;  // a launch of this call ran the block-sparse wide kernel
@@ -2424,7 +2425,8 @@ int run_persist(wrnn_handle* h, int S, wrnn_progress_fn cb, void* user) {
                     awr.p1taps = W.p1taps + (size_t)h->hop * 8;  // the [hop][4] table
                     awr.p1split = W.p1split;
                     le = L.nr > kPWideRows ? launch_persist_wide_gen32_ring(awr, st)
-                                           : launch_persist_wide_gen_ring(awr, st);
+                         : L.rot >= 0  ? launch_persist_wide_gen_rot(awr, st)  // time-sliced (its row map)
+                                       : launch_persist_wide_gen_ring(awr, st);
                 } else if (L.nr > kPWideRows) {
                     return fail(WRNN_ERR_INVALID, "32-row wide launch in a call with P1 / noise streams");
                 } else {
@@ -2802,6 +2804,14 @@ int generate_impl(wrnn_handle* h, int n_utts, const float* const* mels, const in
     }
     pin.gen32 = wide_rows == kPWideGen32Rows && gen_frames && gen_ring_sw != 0 &&
                 persist_wide_gen32_usable(h->cfg.mode);
+    // time-sliced launches (wrnn_set_gen_wide_slices, env WRNN_GEN_SLICE=0|1 read per call): under
+    // the same conditions, for the head's time-sliced instance
+    bool slices = h->gen_wide_slices;
+    if (const char* env = std::getenv("WRNN_GEN_SLICE")) {
+        if (!std::strcmp(env, "0")) slices = false;
+        if (!std::strcmp(env, "1")) slices = true;
+    }
+    pin.gen_slices = slices && gen_frames && gen_ring_sw != 0 && persist_wide_gen_rot_usable(h->cfg.mode);
     plan_call(pin, h->rates, pout);
     const auto& lplan = pout.lplan;
     const int Bplan = pout.Bplan;
@@ -3277,6 +3287,15 @@ int wrnn_set_gen_wide_rows(wrnn_handle* h, int rows) {
     if (rows == kPWideGen32Rows && h->cfg.model_type != WRNN_MODEL_GENEING)
         return fail(WRNN_ERR_INVALID, "32-row wide launches exist for the geneing topology only");
     h->gen_wide_rows = rows;
+    return WRNN_OK;
+}
+
+int wrnn_set_gen_wide_slices(wrnn_handle* h, int on) {
+    if (!h) return fail(WRNN_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(WRNN_ERR_INVALID, "time-sliced wide launches: 0 (off) or 1 (on)");
+    if (on && h->cfg.model_type != WRNN_MODEL_GENEING)
+        return fail(WRNN_ERR_INVALID, "the time-sliced wide launches are opt-in for the geneing topology only");
+    h->gen_wide_slices = on != 0;
     return WRNN_OK;
 }
 

@@ -396,9 +396,9 @@ struct PersistGenArgs {
     uint32_t k0, k1;        // Philox key (BETA draws in-kernel)
     int prog_base;
     DbgLogits dbg;
-    // rotated launch (BITS / MOL; null otherwise): virtual row v = g + 8 r ->
-    // (physical row, step offset), `rows` the launch's RowInfo table by virtual row, rows and
-    // steps per group
+    // rotated launch (BITS / MOL) or time-sliced wide launch (§3.0f; null
+    // otherwise): virtual row v = g + 8 r -> (physical row, step offset), `rows` the launch's
+    // RowInfo table by virtual row; rotated: rows and steps per group
     const int2* vmap;
     const int* gnr;
     const int* giters;
@@ -430,6 +430,13 @@ size_t persist_wide_gen_wreg_floats();
 hipError_t persist_wide_gen_reset_xbuf(float* xbuf, hipStream_t s);
 int persist_wide_gen_scratch(int mode);  // scratch bytes of the mode's stream instances (0 BITS, 1 MOL, 2 BETA)
 int persist_wide_gen_ring_scratch(int mode);  // ... of its ring instances (a ring launch needs 0)
+// Time-sliced ring launch of the 16-row wide kernel (k_persist_wide_gen_rot):
+// t1 <= S steps over the rows of a.vmap, each from its chunk state (a.st) and step offset; a.rows
+// is the launch's RowInfo table by virtual row (rb must be 0). Refused without the frame tables or the map, or
+// when the head's instance is outside its scratch rule (none; Beta at most its 16-byte frame).
+hipError_t launch_persist_wide_gen_rot(const PersistGenRingArgs& a, hipStream_t s);
+int persist_wide_gen_rot_scratch(int mode);  // scratch bytes of the mode's time-sliced instances (-1: none)
+bool persist_wide_gen_rot_usable(int mode);
 int wide_gen_layout_check(int rows_per_group);
 // host: violations of the MOL (30) / BETA (2) logit-pair layout; -1 for bad arguments
 int wide_gen_mol_layout_check(int rows_per_group, int n_logits);

@@ -44,6 +44,7 @@ EXPORTED = [
     'wrnn_debug_wide_gen_mol_layout', 'wrnn_sparse_info', 'wrnn_set_rates', 'wrnn_get_rates', 'wrnn_debug_plan',
     'wrnn_stream_info', 'wrnn_debug_stream_bytes', 'wrnn_set_gen_wide_rows', 'wrnn_debug_wide_gen32_layout',
     'wrnn_debug_wide_gen32_mol_layout', 'wrnn_debug_wide_sp_pack', 'wrnn_debug_wide_sp_image', 'wrnn_sparse_wide_info',
+    'wrnn_set_gen_wide_slices',
 ]
 
 
@@ -121,6 +122,7 @@ def load_library(path=None):
                                                P(c_int), P(c_int), PROGRESS_FN, c_void_p]),
         'wrnn_set_engine': (c_int, [c_void_p, c_int]),
         'wrnn_set_gen_wide_rows': (c_int, [c_void_p, c_int]),
+        'wrnn_set_gen_wide_slices': (c_int, [c_void_p, c_int]),
         'wrnn_last_engine': (c_int, [c_void_p, P(c_int)]),
         'wrnn_fallback_info': (c_int, [c_void_p, P(c_int), ctypes.c_char_p, c_size_t]),
         'wrnn_enable_stage_timing': (c_int, [c_void_p, c_int]),

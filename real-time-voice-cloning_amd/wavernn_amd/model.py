@@ -217,6 +217,14 @@ class WaveRNN:
         that is not geneing. Env WRNN_GEN_WIDE_ROWS=16|32 overrides it per call."""
         _abi.check(self._lib.wrnn_set_gen_wide_rows(self._h, int(rows)))
 
+    def set_wide_slices(self, on):
+        """Time-sliced wide launches of a geneing model for later calls (default off): a call of
+        more than 16 rows per XCD group, not a multiple of 16, may run as launches of 16 rows per
+        group over rotating row sets when the rate table prices that cheaper; same results bit for
+        bit. ValueError when switched on for a model that is not geneing. Env WRNN_GEN_SLICE=0|1
+        overrides it per call."""
+        _abi.check(self._lib.wrnn_set_gen_wide_slices(self._h, 1 if on else 0))
+
     def last_engine(self):
         """Engine ('chain' or 'persist') that ran the last call."""
         e = ctypes.c_int()

@@ -25,6 +25,11 @@ time) and writes `key v1 .. v4` lines for the keys it found; the runtime
     MOL / Beta, one 32-row launch at k = 17 .. 32 rows per group, WRNN_PERSIST_WIDE=1 and
     WRNN_GEN_WIDE_ROWS=32; at least two fills) -> wide_gen32, wide_gen32_mol, wide_gen32_beta = base,
     per row (least squares)
+  <dir>/gen_slice_r16.log, <dir>/gen_slice_mol_r16.log, <dir>/gen_slice_beta_r16.log (geneing BITS / MOL /
+    Beta, a time-sliced call, WRNN_GEN_SLICE=1: `us_per_step` is the mean step of its launches, which
+    run 16 rows per group but for the short tails) -> wide_gen_slice, wide_gen_slice_mol,
+    wide_gen_slice_beta = base, per row: one fill, so the per-row term is that of the head's unsliced
+    key (wide_gen, wide_gen_mol, wide_gen_beta), from this pass or else from the table given as OUT
   <dir>/sp_wide_r<k>.log, <dir>/sp10_wide_r<k>.log (fatchord RAW at 9 / 10 bits on 90 %-pruned weights,
     every launch block-sparse wide at k rows per group, WRNN_PERSIST_WIDE=1 and WRNN_SPARSE_WIDE=1), or
     <dir>/rates.log (stage-timing lines {"bits", "rows_per_group", "kernel", "us_per_step"}; the
@@ -39,6 +44,19 @@ import os
 import sys
 
 FAMILIES = {'nr': 'fat9', 'u10_nr': 'fat10', 'sp_nr': 'fat9_sp', 'rr_nr': 'rr', 'gen_nr': 'gen'}
+
+
+def table_of(path):
+    """{key: [values]} of the key lines of a rate table (none when there is no such file)."""
+    tab = {}
+    try:
+        for ln in open(path):
+            k = ln.split('#')[0].split()
+            if k:
+                tab[k[0]] = [float(v) for v in k[1:]]
+    except OSError:
+        pass
+    return tab
 
 
 def line_of(path):
@@ -115,6 +133,20 @@ def main():
                 per_row = max(per_row, 0.001)
                 keys[key] = [round(mv - per_row * mk, 3), round(per_row, 4)]
                 src[key] = d
+        for pre, key, head in (('gen_slice_r', 'wide_gen_slice', 'wide_gen'),
+                               ('gen_slice_mol_r', 'wide_gen_slice_mol', 'wide_gen_mol'),
+                               ('gen_slice_beta_r', 'wide_gen_slice_beta', 'wide_gen_beta')):
+            # one fill: every sliced launch but the short tails runs 16 rows per group. The per-row
+            # term is the head's unsliced key's, of this pass or else of the table given as OUT
+            v16 = us_step(line_of(os.path.join(d, f'{pre}16.log')))
+            if v16 is None:
+                continue
+            unsliced = keys.get(head) or table_of(out).get(head)
+            if not unsliced or len(unsliced) != 2:
+                print(f'{key}: skipped, no {head} key in this pass or in {out}', file=sys.stderr)
+                continue
+            keys[key] = [round(v16 - unsliced[1] * 16, 3), unsliced[1]]
+            src[key] = d
         pts = [(k, us_step(line_of(os.path.join(d, f'sp_wide_r{k}.log')))) for k in range(1, 17)]
         pts = [(k, v) for k, v in pts if v is not None]
         pts10 = [(k, us_step(line_of(os.path.join(d, f'sp10_wide_r{k}.log')))) for k in range(1, 17)]

@@ -30,7 +30,9 @@ HEADS = [('fat_raw9', FAT, 9, RAW), ('fat_raw10', FAT, 10, RAW), ('fat_mol', FAT
          ('rr_raw9', RR, 9, RAW), ('rr_raw10', RR, 10, RAW), ('rr_mol', RR, 9, MOL),
          ('gen_raw9', GEN, 9, RAW), ('gen_raw10', GEN, 10, RAW), ('gen_mol', GEN, 9, MOL),
          ('gen_beta', GEN, 9, BETA)]
-TOPO_BITS = {FAT: (1, 2, 4, 8), RR: (2, 4, 16), GEN: (4, 32, 64, 128, 256)}
+# (1024, the geneing time-sliced instances, came after the other nine: its flag sets are further
+# lines, and every line of a set without it stays what it was)
+TOPO_BITS = {FAT: (1, 2, 4, 8), RR: (2, 4, 16), GEN: (4, 32, 64, 128, 256, 1024)}
 ALL_BITS = 511
 ROWS = list(range(1, 73)) + [131, 144, 152, 232, 360, 2115, 4096]
 ROWS_RATE = [8, 18, 33, 45, 144, 232, 360]
@@ -44,6 +46,7 @@ SHIPPED = {
     'wide_rr_mol': [9.285, 0.0321], 'wide_gen': [3.508, 0.0082], 'wide_gen_mol': [3.025, 0.0094],
     'wide_gen_beta': [4.84, 0.033], 'wide_gen32': [6.347, 0.0066], 'wide_gen32_mol': [3.992, 0.0222],
     'wide_gen32_beta': [6.001, 0.0835], 'slice': [60.0, 0.98],
+    'wide_gen_slice': [3.46, 0.0082], 'wide_gen_slice_mol': [2.797, 0.0094], 'wide_gen_slice_beta': [4.728, 0.033],
     'rot9': [4.8, 5.22, 5.91, 6.92], 'rot9_sp': [4.99, 6.95, 7.99, 9.26], 'rot_mol3_lo': [4.70],
     'rot_rr9': [6.3, 7.0, 7.78, 8.8], 'rot_rr10': [6.5, 7.26, 8.14, 9.23],
     'rot_rrm': [5.9, 6.6, 7.42, 8.4], 'rot_gen': [1.98, 2.47, 3.12, 3.64],
@@ -105,7 +108,8 @@ class Dump:
             for scale in (0.25, 4.0):
                 table = key + ' ' + ' '.join(repr(v * scale) for v in vals)
                 for name, model, bits, mode in HEADS:
-                    for flags in (sum(TOPO_BITS[model]), ALL_BITS):
+                    every = sum(TOPO_BITS[model])
+                    for flags in (every & ~1024, ALL_BITS) + ((every,) if every & 1024 else ()):
                         for rows in ROWS_RATE:
                             for S in SEQ:
                                 print(f'rate {key}x{scale} {name} flags={flags} rows={rows} S={S}: '
