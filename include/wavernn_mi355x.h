@@ -441,6 +441,52 @@ int wrnn_debug_p1(wrnn_handle* h, int step, int row, float* out, size_t capacity
 int wrnn_set_debug_steps(wrnn_handle* h, const int* steps, int n);
 int wrnn_debug_logits(wrnn_handle* h, int step, int row, float* out, size_t capacity);
 
+/* Streaming sessions (no reference equivalent): mel frames in as they arrive,
+ * labels out as soon as their conditioning is final. Over its lifetime a session produces exactly
+ * n_frames * hop_length labels, and they equal the single row of wrnn_generate(batched = 0) on the
+ * same mel, seed and noise stream bit for bit, however the frames were cut into pushes.
+ * Fatchord (rnn_dims = fc_dims = 512), RAW, at most 1024 classes, on the PERSIST engine with the
+ * per-frame conditioning form; every other handle (runtimeracer, geneing, MOL, a handle forced to
+ * CHAIN, a device the persistent engine cannot run on) is refused at wrnn_stream_open with
+ * WRNN_ERR_INVALID. A pruned model runs on its dense instances (same results).
+ *
+ * wrnn_stream_open: a session for at most max_frames frames with its own device memory (frame
+ * tables, chunk state, outputs; DESIGN.md §3.0i has the bytes per frame). It takes the handle's
+ * seed as it is now and the handle's next noise stream id, advancing that counter by one (so
+ * wrnn_set_stream before the call selects the id). Allocation failure: WRNN_ERR_OOM.
+ * wrnn_stream_push: n_frames more frames, host float32 (feat_dims, n_frames) row-major, normalised
+ * as for wrnn_generate; last != 0 ends the utterance (n_frames = 0 is then allowed). Frames past
+ * max_frames: WRNN_ERR_CAPACITY, nothing changes. A push after the last one: WRNN_ERR_INVALID.
+ * wrnn_stream_advance: runs every ready step of up to 8 distinct sessions of one handle in one
+ * launch, one session per XCD group, each with its own step count; a session with nothing ready
+ * sits out, and when nothing is ready anywhere no kernel is launched. Session i's new labels go to
+ * labels[i] (host, capacity[i] entries) and their count to n_out[i]. A capacity below what is
+ * ready: WRNN_ERR_CAPACITY and nothing runs. n > 8, a session listed twice or sessions of
+ * different handles: WRNN_ERR_INVALID. There is no progress callback.
+ * Readiness: steps_ready = last ? frames * hop : max(0, frames - lookahead) * hop, with the
+ * look-ahead max(pad, reach of the in-kernel upsampler taps) frames (2 for the shipped
+ * hyper-parameters); wrnn_debug_stream_ready is that rule, host only, and the runtime's own.
+ * wrnn_stream_status: any pointer may be null. (wrnn_stream_info is the older per-call
+ * introspection above.)
+ * The handle's other calls keep working while sessions are open and do not disturb them;
+ * wrnn_destroy closes the handle's open sessions. */
+typedef struct wrnn_stream wrnn_stream;
+int wrnn_stream_open(wrnn_handle* h, int max_frames, wrnn_stream** out);
+int wrnn_stream_push(wrnn_stream* s, const float* mel, int n_frames, int last);
+int wrnn_stream_advance(wrnn_stream* const* ss, int n, int16_t* const* labels, const size_t* capacity,
+                        size_t* n_out);
+int wrnn_stream_status(wrnn_stream* s, int* frames_pushed, int* ended, int64_t* steps_done,
+                       int64_t* steps_ready, int* lookahead_frames);
+void wrnn_stream_close(wrnn_stream* s);
+int wrnn_debug_stream_ready(int frames, int last, int hop, int lookahead, int64_t* steps);
+/* Copy-out of one frame's conditioning row (tests): table 0 = the P1 mel projection, 1 = the P1
+ * aux projection (4 * rnn_dims floats each), 2 = the per-frame conditioning row of the later
+ * layers; frame -1 is the zero frame. wrnn_debug_stream_row reads a session's tables (a row that is
+ * not final yet holds NaN), wrnn_debug_frame_row those of utterance 0 of the handle's last
+ * persistent call. *width receives the row's floats; capacity below it: WRNN_ERR_CAPACITY. */
+int wrnn_debug_stream_row(wrnn_stream* s, int frame, int table, float* out, size_t capacity, int* width);
+int wrnn_debug_frame_row(wrnn_handle* h, int frame, int table, float* out, size_t capacity, int* width);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,11 @@ __device__ __forceinline__ ARow a_row(const GemmA& a, int m, int M) {
         r.o1 = (long)(a.r_off - a.n_mel) * a.ldr + p / a.hop;
         r.s1 = a.ldr;
         r.ksplit = a.n_mel;
+    } else if constexpr (AK == 3) {  // frame window: row m = frame m of a.R (no zero-frame slot)
+        r.p0 = r.p1 = a.R;
+        r.o0 = r.o1 = (long)a.r_off * a.ldr + m;
+        r.s0 = r.s1 = a.ldr;
+        r.ksplit = 1 << 30;
     } else {  // frame-A: slot 0 is the zero frame; slot f+1 = frame f
         r.zero |= m == 0;
         r.p0 = r.p1 = a.R;
@@ -194,6 +199,8 @@ static void launch_nt(dim3 grid, int M, int N, int K, const GemmA& a, const Gemm
         hipLaunchKernelGGL((k_gemm<NT, 0, BK>), grid, dim3(kThreads), 0, s, M, N, K, a, b, e);
     else if (a.kind == 1)
         hipLaunchKernelGGL((k_gemm<NT, 1, BK>), grid, dim3(kThreads), 0, s, M, N, K, a, b, e);
+    else if (a.kind == 3)
+        hipLaunchKernelGGL((k_gemm<NT, 3, BK>), grid, dim3(kThreads), 0, s, M, N, K, a, b, e);
     else
         hipLaunchKernelGGL((k_gemm<NT, 2, BK>), grid, dim3(kThreads), 0, s, M, N, K, a, b, e);
 }
@@ -201,7 +208,7 @@ static void launch_nt(dim3 grid, int M, int N, int K, const GemmA& a, const Gemm
 hipError_t launch_gemm(int M, int N, int K, const GemmA& a, const GemmB& b, const GemmEp& e,
                        hipStream_t s) {
     if (M <= 0 || N <= 0) return hipSuccess;
-    if (a.kind < 0 || a.kind > 2) return hipErrorInvalidValue;
+    if (a.kind < 0 || a.kind > 3) return hipErrorInvalidValue;
     const int m_tiles8 = ((M + 63) / 64 + 7) / 8 * 8;  // k_gemm's XCD-aware tile order
     if (N >= 1024)  // wide outputs (P1: 3H / 4H columns): 4 column tiles per workgroup
         launch_nt<kGemmWideNT, 16>(

@@ -142,7 +142,10 @@ constexpr int hh2_rowmask(int win, int nr) {
 //      per-position lookup follows; noise, labels, samples, state and logits use the physical
 //      row and the offset step.
 // SP: the sparse instance (pruned weights, block lists in LDS; sp_products above)
-template <int NR, bool FC3R, bool MOL, bool P1R, bool ROT, bool DBG, bool SP>
+// STRM: a streaming launch (launch_persist_stream: ROT, one row, the group's own buffers). The
+//      GRU1 of the step after the group's last one is left to the session's next launch -- the
+//      P1 row it needs may not be final yet -- so its operands are saved beside the chunk state.
+template <int NR, bool FC3R, bool MOL, bool P1R, bool ROT, bool DBG, bool SP, bool STRM = false>
 __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, const int g, const int w) {
     static_assert(!ROT || P1R, "rotated launches form P1 in the ring");
     static_assert(!SP || P1R, "sparse instances form P1 in the ring");
@@ -201,7 +204,10 @@ __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, c
     const bool own = gate_a && kc < NR;
     const int lr = kc < NR ? kc : 0;
     // physical row / step offset of row slot r (identity / 0 unless rotated)
-    auto vmap_g = [&](int r) -> int2 { return ROT ? a.vmap[g0 + kPG * r] : make_int2(g0 + kPG * r, 0); };
+    // (STRM: row 0 of the session's own buffers, the step offset in its RowInfo alone)
+    auto vmap_g = [&](int r) -> int2 {
+        return STRM ? make_int2(0, 0) : ROT ? a.vmap[g0 + kPG * r] : make_int2(g0 + kPG * r, 0);
+    };
     const int2 lvm = vmap_g(lr);
     const int lrow = lvm.x;  // (physical) row of this lane's epilogue
 #pragma unroll
@@ -233,7 +239,8 @@ __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, c
     const unsigned o_y = (unsigned)(lr * kPH + u) * 8u;                 // bufB/C pair (row lr, unit u)
     // gumbel row lrow (a padding row reads row rb's: no HBM traffic for padding); a rotated
     // launch reads its rows' steps off + t: the offset folded into the lane's base
-    const unsigned o_gum = ROT ? (unsigned)(((lvm.y * a.B) + lrow) * a.n_classes + cls) * 4u
+    const unsigned o_gum = STRM ? (unsigned)cls * 4u
+                           : ROT ? (unsigned)(((lvm.y * a.B) + lrow) * a.n_classes + cls) * 4u
                                : (unsigned)((lrow < a.nreal ? lrow : a.rb) * a.n_classes + cls) * 4u;
     const rsrc_t fcr = mk_rsrc(a.fcond);
     __syncthreads();
@@ -282,7 +289,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, c
         const RowInfo& ri = reinterpret_cast<const RowInfo*>(lds + L_RI)[kx >> 2];
         // (a row's own steps end at S: a rotated row at offset off reads P1 up to S - 1 - off;
         // the P1 of the step after the launch's last one feeds the GRU1 whose state is saved)
-        const int lim = ROT ? a.S - reinterpret_cast<const int2*>(lds + L_VM)[kx >> 2].y : a.S;
+        const int lim = ROT && !STRM ? a.S - reinterpret_cast<const int2*>(lds + L_VM)[kx >> 2].y : a.S;
         tau = tau < lim ? tau : lim - 1;
         const unsigned p = (unsigned)(ri.rel0 + tau);
         const bool in = p < (unsigned)ri.L;  // else the zero tail pad: bias only (zero frame)
@@ -858,7 +865,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, c
                     if (w == 0) {
                         int rr = r;  // (recomputed per step: a hoisted offset costs a register)
                         asm volatile("" : "+v"(rr));
-                        const int2 vm = reinterpret_cast<const int2*>(lds + L_VM)[rr];
+                        const int2 vm = STRM ? make_int2(0, 0) : reinterpret_cast<const int2*>(lds + L_VM)[rr];
                         const unsigned ro = (unsigned)(vm.x * a.ld + vm.y);
                         __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bi, mk_rsrc(a.labels),
                                                               ro * 2u, (unsigned)t * 2u, 0);
@@ -934,6 +941,9 @@ __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, c
         // ================= GRU1 of step t+1 for all 512 units (redundant) ===================
         //   gi = W_ih1 (cI + w0 x) + b_ih1 = P1 + v x ; x1 = (cI + w0 x) + h1
         const float w0j = lds[L_W0 + tid];
+        // (STRM: the GRU1 after the group's last step is the next launch's -- its P1 may not be
+        // final yet; h1 stays as it is for the save below)
+        if (!STRM || t != t1g - 1)
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             const float x = lds[L_SX + r];
@@ -944,7 +954,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, c
             lds[L_X1 + r * kPH + tid] = hn;
         }
         pgum = pgn;
-        if (w == 0 && tid == 0) {
+        if (!STRM && w == 0 && tid == 0) {  // (a streaming launch has no progress callback)
             // (rotated: the launch's share of the call, steps scaled to S per launch)
             if (g == 0) p_progress(a.progress, a.prog_base, ROT ? (int)((long long)t * a.S / t1g) : t, t);
             if (p_abort(a.ctl, a.progress, t)) lds[L_FAIL] = 1.f;  // seen after the next sample
@@ -957,6 +967,21 @@ __device__ __forceinline__ void persist_body(const PersistArgs& a, float* lds, c
     if (a.stamps && g == 0 && w == 0 && tid == 0) a.stamps[1] = p_now();
     // ---- save the chunk state --------------------------------------------------------------
     // (addresses recomputed here: values kept alive across the step loop cost registers)
+    if constexpr (STRM) {
+        // the next launch's GRU1 operands (k_persist_stream_resume): h1 before that GRU1, gh1 of
+        // the last step (still in the exchange area: every slot saw it drained, gru1_loads) and
+        // the last sample; x1 / h1 of the state saved below are stale and replaced from these
+        if (w == 0 && t1g > a.t0) {
+            float* sv = a.st_gh2 + 3 * H;
+            const u4v v = __builtin_amdgcn_raw_buffer_load_b128(
+                xr, o_tid * 4u, (unsigned)(XB_G + (((t1g - 1) & 1) * kPNR) * kPH * 4) * 4u, kCpNT);
+            sv[tid] = h1[0];
+            sv[H + tid] = __uint_as_float(v.x);
+            sv[2 * H + tid] = __uint_as_float(v.y);
+            sv[3 * H + tid] = __uint_as_float(v.z);
+            if (tid == 0) sv[4 * H] = lds[L_SX];
+        }
+    }
     if (ROT || a.t1 < a.S) {
         int tx = tid;
         asm volatile("" : "+v"(tx));
@@ -992,7 +1017,25 @@ __global__ __launch_bounds__(kPT, 1) void k_persist(PersistArgs a) {
     if (!s_ok) return;
     const int g = __builtin_amdgcn_readfirstlane(s_group);
     const int w = __builtin_amdgcn_readfirstlane(s_slot);
-    if constexpr (ROT && NR > 1) {
+    if constexpr (ROT && NR == 1) {
+        // streaming launch (launch_persist_stream): group g runs one row of the session
+        // a.sgroup[g] on that session's own buffers; a group without steps sits out (nothing
+        // polls another group's exchange area, so its workgroups just leave after registering)
+        if (__builtin_amdgcn_readfirstlane(a.giters[g]) <= 0) return;
+        const StreamGroup* sg = a.sgroup + g;
+        PersistArgs b = a;
+        b.p1q = sg->p1q;
+        b.p1a = sg->p1a;
+        b.fcond = sg->fcond;
+        b.gumbel = sg->gumbel;
+        b.labels = sg->labels;
+        b.samples = sg->samples;
+        b.st_x1 = sg->st;
+        b.st_h1 = sg->st + kPH;
+        b.st_h2 = sg->st + 2 * kPH;
+        b.st_gh2 = sg->st + 3 * kPH;
+        persist_body<1, FC3R, MOL, P1R, true, DBG, SP, true>(b, lds, g, w);
+    } else if constexpr (ROT && NR > 1) {
         // a rotated launch holds groups of NR and of NR - 1 rows: each runs its own body
         if (__builtin_amdgcn_readfirstlane(a.gnr[g]) == NR)
             persist_body<NR, FC3R, MOL, P1R, true, DBG, SP>(a, lds, g, w);
@@ -1273,5 +1316,28 @@ hipError_t launch_persist(const PersistArgs& a, hipStream_t s) {
     }
 }
 #endif  // WRNN_PERSIST_PART != 2
+
+#if WRNN_PERSIST_PART != 1
+// ---- streaming sessions (stream.hip) ------------------------------------------
+// The streaming instances: k_persist<1, FC3R, RAW, ring, ROT> (no other launch takes ROT with one
+// row per group). Built with the MOL part, under the default machine scheduler: with iterative ILP
+// the 1024-class instance spills 4 VGPRs.
+hipError_t launch_persist_stream(const PersistArgs& a, hipStream_t s) {
+    if (!a.sgroup || !a.vmap || !a.giters || !a.rows || !a.p1taps || a.hop <= 0 || a.B != 1 || a.nr != 1 ||
+        a.rb != 0 || a.t0 != 0 || a.mode != 0 || a.sparse || a.cpw < 1 || a.cpw > kPCls ||
+        a.cpw * kPM < a.n_classes)
+        return hipErrorInvalidValue;
+    if (a.cpw > 16) return persist_launch<k_persist<1, true, false, true, true, false>>(persist_lds_bytes(), a, s);
+    return persist_launch<k_persist<1, false, false, true, true, false>>(persist_lds_bytes(), a, s);
+}
+
+int persist_stream_scratch(int cpw) {
+    hipFuncAttributes fa;
+    const void* f = cpw > 16 ? (const void*)k_persist<1, true, false, true, true, false>
+                             : (const void*)k_persist<1, false, false, true, true, false>;
+    if (hipFuncGetAttributes(&fa, f) != hipSuccess) return -1;
+    return (int)fa.localSizeBytes;
+}
+#endif  // WRNN_PERSIST_PART != 1
 
 }  // namespace wrnn

@@ -263,6 +263,9 @@ struct wrnn_handle {
     };
     std::vector<PStage> pstages;  // launch kinds of the last PERSIST call
     double p_avg_steps = 0;                      // steps per timed launch
+    // ---- streaming sessions (stream.hip): the open sessions, the per-launch group table
+    std::vector<struct wrnn_stream*> sessions;
+    DevBuf stream_tab;
 
     ~wrnn_handle() {
         for (auto e : pev) (void)hipEventDestroy(e);
@@ -3095,6 +3098,7 @@ void wrnn_destroy(wrnn_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
+    while (!h->sessions.empty()) wrnn_stream_close(h->sessions.back());  // (stream.hip)
     delete h;
 }
 
@@ -3625,3 +3629,7 @@ int wrnn_debug_p1(wrnn_handle* h, int step, int row, float* out, size_t capacity
 }
 
 }  // extern "C"
+
+// The streaming sessions (wrnn_stream_*): a file of their own, compiled as part of this
+// translation unit because they work on the handle defined above.
+#include "stream.hip"

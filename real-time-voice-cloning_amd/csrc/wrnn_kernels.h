@@ -110,7 +110,8 @@ struct SampleArgs {
 // D[m][n] = sum_k A(m,k) * B(k,n), epilogue per element.
 // ---------------------------------------------------------------------------------------
 struct GemmA {  // A(m, k)
-    int kind;   // 0: row-major W[m*ld + k]; 1: cond-A (mel/aux gather for cI); 2: frame-A
+    int kind;   // 0: row-major W[m*ld + k]; 1: cond-A (mel/aux gather for cI); 2: frame-A;
+                // 3: frame-A without the zero-frame slot (row m = frame m: a window of frames)
     const float* p;
     int ld;
     // kind 1: row m = (fold f = m / S, step t = m % S), S = M / Bu -> position p = f * tpo + t;
@@ -255,9 +256,41 @@ struct PersistArgs {
     // sparse instance (k_persist only; P1 ring): wreg = [kPM][kPT] uint4 per-lane masks / list
     // bases, wlds = [kPM][kPLdsW4] float4 block lists (runtime.hip pack_persist_sparse)
     int sparse;
+    // streaming launch (launch_persist_stream; null otherwise): group g runs the session sgroup[g]
+    const struct StreamGroup* sgroup;
 };
 
+// One XCD group of a streaming launch (stream.hip): the buffers of the session
+// it runs -- each session owns its frame tables, noise window, outputs and chunk state -- and
+// the step window [step0, step0 + steps) of this launch (steps 0: the group sits out).
+struct StreamGroup {
+    const float* p1q;     // frame tables as PersistArgs::p1q / p1a / fcond (fbase = 1)
+    const float* p1a;
+    const float* fcond;
+    float* gumbel;        // [steps][n] noise of the window (k_gumbel_stream)
+    int16_t* labels;      // [steps] the window's labels ...
+    float* samples;       // ... and samples
+    float* st;            // chunk state, kStreamState floats: x1, h1, h2 (H each), gh2 (3H) as
+                          // PersistArgs::st_*; then the GRU1 operands of step0 + steps, which the
+                          // session's next launch forms: h1 before it (H), gh1 (3H), the sample
+    const float* P1;      // [4H] P1 of step0 (k_p1_expand; k_persist_init / the resume kernel)
+    int step0, steps;
+    uint32_t stream;      // Philox counter word 3 ...
+    uint32_t k0, k1;      // ... and key (the seed the session took at wrnn_stream_open)
+    int pad_;
+};
+constexpr int kStreamState = 10 * kPH + 4;
+
 hipError_t launch_persist(const PersistArgs& a, hipStream_t s);
+// Streaming launch of k_persist: one session per XCD group (a.sgroup[g], one row), rotated form
+// with a.vmap[g] = (0, 0), a.giters[g] = the group's steps, a.rows[g] the session's RowInfo with
+// rel0 = step0; RAW, P1 ring. a.B must be 1.
+hipError_t launch_persist_stream(const PersistArgs& a, hipStream_t s);
+int persist_stream_scratch(int cpw);  // scratch bytes of the streaming instance (-1: query error)
+// x1 / h1 of step0 > 0 of every running group from the saved GRU1 operands and sg[g].P1
+hipError_t launch_stream_resume(const StreamGroup* sg, int n, const float* v, const float* w0, hipStream_t s);
+// noise of every running group's window: steps step0 .. step0 + steps - 1 of its stream
+hipError_t launch_gumbel_stream(const StreamGroup* sg, int n, int max_steps, int n_classes, hipStream_t s);
 // Wide-row fatchord launch: up to kPWideRows rows per XCD group (8 kPWideRows per launch),
 // fp32 MFMA products, RAW categorical with <= 1024 classes (> 512: PersistArgs::wfc3b).
 hipError_t launch_persist_wide(const PersistArgs& a, hipStream_t s);

@@ -45,6 +45,8 @@ EXPORTED = [
     'wrnn_stream_info', 'wrnn_debug_stream_bytes', 'wrnn_set_gen_wide_rows', 'wrnn_debug_wide_gen32_layout',
     'wrnn_debug_wide_gen32_mol_layout', 'wrnn_debug_wide_sp_pack', 'wrnn_debug_wide_sp_image', 'wrnn_sparse_wide_info',
     'wrnn_set_gen_wide_slices',
+    'wrnn_stream_open', 'wrnn_stream_push', 'wrnn_stream_advance', 'wrnn_stream_status', 'wrnn_stream_close',
+    'wrnn_debug_stream_ready', 'wrnn_debug_stream_row', 'wrnn_debug_frame_row',
 ]
 
 
@@ -170,6 +172,15 @@ def load_library(path=None):
         'wrnn_debug_wide_gen32_layout': (c_int, [c_int]),
         'wrnn_debug_wide_gen32_mol_layout': (c_int, [c_int, c_int]),
         'wrnn_debug_logits': (c_int, [c_void_p, c_int, c_int, P(ctypes.c_float), c_size_t]),
+        'wrnn_stream_open': (c_int, [c_void_p, c_int, P(c_void_p)]),
+        'wrnn_stream_push': (c_int, [c_void_p, P(ctypes.c_float), c_int, c_int]),
+        'wrnn_stream_advance': (c_int, [P(c_void_p), c_int, P(c_void_p), P(c_size_t), P(c_size_t)]),
+        'wrnn_stream_status': (c_int, [c_void_p, P(c_int), P(c_int), P(ctypes.c_int64), P(ctypes.c_int64),
+                                       P(c_int)]),
+        'wrnn_stream_close': (None, [c_void_p]),
+        'wrnn_debug_stream_ready': (c_int, [c_int, c_int, c_int, c_int, P(ctypes.c_int64)]),
+        'wrnn_debug_stream_row': (c_int, [c_void_p, c_int, c_int, P(ctypes.c_float), c_size_t, P(c_int)]),
+        'wrnn_debug_frame_row': (c_int, [c_void_p, c_int, c_int, P(ctypes.c_float), c_size_t, P(c_int)]),
         'wrnn_debug_wide_sp_pack': (c_int, [P(ctypes.c_float), c_int, c_int, c_int, P(ctypes.c_float), P(c_int),
                                             P(c_int)]),
         'wrnn_debug_wide_sp_image': (c_int, [P(ctypes.c_float), c_int, P(ctypes.c_float), P(ctypes.c_float),

@@ -165,6 +165,70 @@ def postprocess_labels(labels, target, overlap, mu_law, apply_preemphasis, n_cla
     return out
 
 
+class StreamPost:
+    """postprocess(batched=False) of categorical labels carried over chunks (streaming sessions,
+    DESIGN.md §3.0i): label -> sample with the one-shot formula, mu-law decode, de-emphasis with
+    its one-sample state carried, then the one-shot tail -- ``output[:wave_len]`` with
+    ``wave_len = (T - 1) * hop`` and the fade over its last ``20 * hop`` samples. Neither is known
+    before the end, so the last ``20 * hop + hop`` processed samples are held back until
+    ``finish``; what ``feed`` returns is final. Concatenated, the chunks equal the one-shot output
+    bit for bit (the same numpy expressions on the same doubles, element for element)."""
+
+    def __init__(self, n_classes, hop_length, mu_law, apply_preemphasis, lib=None):
+        self.n_classes = n_classes
+        self.hop = hop_length
+        self.mu_law = bool(mu_law)
+        self.pre = bool(apply_preemphasis)
+        self.lib = lib
+        self.hold = 20 * hop_length + hop_length
+        self._held = np.empty(0, np.float64)  # processed, not yet yielded
+        self._y_prev = None                   # last de-emphasised sample (the filter's state)
+        self.n_in = 0
+        self.n_out = 0
+        self.finished = False
+
+    def _process(self, labels):
+        x = labels_to_samples(np.asarray(labels, dtype=np.int16), self.n_classes).astype(np.float64)
+        if self.mu_law:
+            x = decode_mu_law(x, self.n_classes, False)
+        if self.pre and x.size:
+            # y[n] = x[n] + c y[n - 1] (lfilter([1], [1, -c])): a chunk continues the recurrence
+            # when the previous output sample is put in front of it (0 + y_prev = y_prev)
+            if self._y_prev is not None:
+                x = np.concatenate([[self._y_prev], x])
+            y = de_emphasis_native(x, self.lib) if self.lib is not None else de_emphasis(x)
+            x = y[1:] if self._y_prev is not None else y
+            self._y_prev = float(x[-1])
+        return x
+
+    def feed(self, labels):
+        """Process a chunk of labels; returns the samples that are final (float64)."""
+        if self.finished:
+            raise ValueError('StreamPost.feed after finish')
+        labels = np.asarray(labels).reshape(-1)
+        self.n_in += labels.size
+        buf = np.concatenate([self._held, self._process(labels)])
+        n = max(0, buf.size - self.hold)
+        out, self._held = buf[:n].copy(), buf[n:].copy()
+        self.n_out += out.size
+        return out
+
+    def finish(self):
+        """The rest of the utterance: cut to (T - 1) * hop samples, the last 20 * hop faded."""
+        if self.finished:
+            raise ValueError('StreamPost.finish called twice')
+        self.finished = True
+        wave_len = self.n_in - self.hop
+        output = self._held[:max(0, wave_len - self.n_out)].copy()
+        fade_out = np.linspace(1, 0, 20 * self.hop)
+        # (samples were yielded only once 21 hops lay behind them, so the fade lies in `output`;
+        # an utterance shorter than the fade fails here as the one-shot expression does)
+        output[-20 * self.hop:] *= fade_out
+        self.n_out += output.size
+        self._held = np.empty(0, np.float64)
+        return output
+
+
 def postprocess(samples, batched, target, overlap, mu_law, apply_preemphasis, n_classes,
                 wave_len, hop_length, labels=None, lib=None):
     """fatchord_version.py:238-255 on the (B, S) per-fold samples (any float dtype).

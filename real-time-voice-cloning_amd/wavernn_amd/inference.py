@@ -97,6 +97,39 @@ def infer_waveform(mel, normalize=True, batched=True, target=None, overlap=None,
     return wav
 
 
+def infer_waveform_stream(mel_chunks, normalize=True, max_frames=None):
+    """Generator: vocode an utterance whose mel arrives in ``(num_mels, n)`` chunks, yielding
+    float64 waveform chunks as soon as they are final. Concatenated, the chunks equal
+    ``infer_waveform(mel, batched=False)`` of the whole mel bit for bit. ``max_frames``: the most
+    frames the utterance can have (default: the chunks are collected first to count them, which
+    gives up the early start -- a live caller passes its bound)."""
+    if _model is None or _model_type is None:
+        raise Exception("Please load Wave-RNN in memory before using it")
+    if _model_type == base.VOC_TYPE_CPP:
+        raise NotImplementedError('streaming needs the checkpoint (MI355X) backend')
+    from .audio import StreamPost
+    hp_wavernn = base.hparams_for(_model_type)
+    if max_frames is None:
+        mel_chunks = [np.asarray(c) for c in mel_chunks]
+        max_frames = max(1, sum(int(c.shape[-1]) for c in mel_chunks))
+    mu_law = hp_wavernn.mu_law if _model.mode == 'RAW' else False
+    post = StreamPost(_model.n_classes, _model.hop_length, mu_law, sp.preemphasize, _model._lib)
+    session = _model.open_stream(max_frames)
+    try:
+        for chunk in mel_chunks:
+            if normalize:  # (the one-shot expressions, element for element)
+                chunk = chunk / sp.max_abs_value
+            wav = post.feed(session.push(np.asarray(chunk, dtype=np.float32)))
+            if wav.size:
+                yield wav
+        wav = post.feed(session.push(None, last=True))
+        if wav.size:
+            yield wav
+        yield post.finish()
+    finally:
+        session.close()
+
+
 def set_seed(seed):
     global _seed
     _seed = seed

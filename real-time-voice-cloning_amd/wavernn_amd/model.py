@@ -59,6 +59,70 @@ def _to_numpy_f32(x):
     return np.ascontiguousarray(np.asarray(x, dtype=np.float32))
 
 
+def _frame_row(fn, handle, frame, table):
+    w = ctypes.c_int()
+    out = np.empty(4096, np.float32)
+    rc = fn(handle, int(frame), int(table), out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            out.size, ctypes.byref(w))
+    _abi.check(rc, 'frame row')
+    return out[:w.value].copy()
+
+
+class WaveRNNStream:
+    """One streaming session (WaveRNN.open_stream): mel chunks in, label chunks out."""
+
+    def __init__(self, model, handle, max_frames):
+        self._model = model  # keeps the handle alive
+        self._lib = model._lib
+        self._s = handle
+        self.max_frames = max_frames
+
+    def push_frames(self, mel, last=False):
+        """Append a (feat_dims, n) chunk of normalised mel frames without running anything."""
+        if self._s is None:
+            raise ValueError('closed stream session')
+        mel = _to_numpy_f32(mel if mel is not None else np.zeros((0, 0), np.float32))
+        if mel.ndim == 3:
+            mel = mel[0]
+        n = int(mel.shape[-1]) if mel.size else 0
+        rc = self._lib.wrnn_stream_push(
+            self._s, mel.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if n else None, n, int(bool(last)))
+        if rc == _abi.WRNN_ERR_CAPACITY:
+            raise BufferError(_abi.last_error())
+        _abi.check(rc, 'stream push')
+
+    def push(self, mel, last=False):
+        """Append a chunk and run every step that became ready; returns the new int16 labels."""
+        self.push_frames(mel, last)
+        return self._model.advance_streams([self])[0]
+
+    def info(self):
+        """dict(frames, ended, steps_done, steps_ready, lookahead)."""
+        if self._s is None:
+            raise ValueError('closed stream session')
+        fr, en, la = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        sd, sr = ctypes.c_int64(), ctypes.c_int64()
+        _abi.check(self._lib.wrnn_stream_status(self._s, ctypes.byref(fr), ctypes.byref(en), ctypes.byref(sd),
+                                                ctypes.byref(sr), ctypes.byref(la)))
+        return dict(frames=fr.value, ended=bool(en.value), steps_done=sd.value, steps_ready=sr.value,
+                    lookahead=la.value)
+
+    def debug_row(self, frame, table):
+        """Conditioning row of ``frame`` (-1: the zero frame): table 0 = p1q, 1 = p1a, 2 = fcond."""
+        return _frame_row(self._lib.wrnn_debug_stream_row, self._s, frame, table)
+
+    def close(self):
+        if self._s is not None and self._model._h is not None and self._model._h.value:
+            self._lib.wrnn_stream_close(self._s)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class WaveRNN:
     def __init__(self, rnn_dims, fc_dims, bits, pad, upsample_factors, feat_dims, compute_dims,
                  res_out_dims, res_blocks, hop_length, sample_rate, mode='RAW', pruning=False,
@@ -371,6 +435,47 @@ class WaveRNN:
                 self._h, int(step), int(r), out[i].ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                 self.n_classes))
         return out
+
+    # --- streaming sessions (wrnn_stream_*) ----------------------------
+    def open_stream(self, max_frames, stream=None):
+        """A streaming session of at most ``max_frames`` mel frames: frames in through
+        ``push``, int16 labels out as soon as their conditioning is final; the labels of the whole
+        utterance equal ``generate_rows(mel, batched=False)`` on the same seed and noise stream
+        bit for bit. ``stream``: the session's noise stream id (default: the handle's next one).
+        Fatchord RAW on the persistent engine only (ValueError otherwise)."""
+        if not self._loaded:
+            raise RuntimeError("Model hasn't been loaded. Call loadWeights first.")
+        if stream is not None:
+            self.set_stream(stream)
+        s = ctypes.c_void_p()
+        _abi.check(self._lib.wrnn_stream_open(self._h, int(max_frames), ctypes.byref(s)), 'open_stream')
+        return WaveRNNStream(self, s, int(max_frames))
+
+    def advance_streams(self, streams):
+        """Run every ready step of up to 8 sessions of this model in one launch (one session per
+        XCD group); returns their new int16 labels, in order (empty where nothing was ready)."""
+        streams = list(streams)
+        n = len(streams)
+        if n == 0:
+            return []
+        for s in streams:
+            if s._s is None:
+                raise ValueError('closed stream session')
+        outs = [np.empty(max(0, s.info()['steps_ready'] - s.info()['steps_done']), np.int16) for s in streams]
+        ss = (ctypes.c_void_p * n)(*[s._s for s in streams])
+        ptrs = (ctypes.c_void_p * n)(*[o.ctypes.data if o.size else None for o in outs])
+        cap = (ctypes.c_size_t * n)(*[o.size for o in outs])
+        got = (ctypes.c_size_t * n)()
+        rc = self._lib.wrnn_stream_advance(ss, n, ptrs, cap, got)
+        if rc == _abi.WRNN_ERR_CAPACITY:
+            raise BufferError(_abi.last_error())
+        _abi.check(rc, 'advance_streams')
+        return [o[:got[i]] for i, o in enumerate(outs)]
+
+    def debug_frame_row(self, frame, table):
+        """Conditioning row of ``frame`` (-1: the zero frame) of utterance 0 of the last persistent
+        call: table 0 = p1q, 1 = p1a, 2 = fcond (float32)."""
+        return _frame_row(self._lib.wrnn_debug_frame_row, self._h, frame, table)
 
     def gen_display(self, i, seq_len, b_size, gen_rate):
         pbar = _progbar(i, seq_len)
